@@ -8,9 +8,10 @@ reset-on-done.  P=50 packages, T=500 (MAPPO/trainer.py:41-47), env seeds
 42 + global env index, actions uint8 uniform in [0, 15) pre-generated on the
 device (Philox, seed 0) -- inputs resident in HBM before the timed region.
 
-A "step" = one ``mdl_step`` over all local envs.  The K timed steps are
-replayed from hipGraphs of G steps each (launch-bound loop; the same kernels
-as eager launches).  value = agent-steps/s over all ranks (weak scaling: 4096
+A "step" = one ``mdl_step`` over all local envs.  The K = ``--steps`` timed steps
+are replayed from hipGraphs of G steps each, plus one graph of the K mod G steps
+left over (launch-bound loop; the same kernels as eager launches).  value =
+agent-steps/s over all ranks (weak scaling: 4096
 envs per GPU, no collective on the step path; ``--total-envs N`` splits N envs
 over the ranks instead: strong scaling, SURVEY.md 8(e), global env ids and seeds
 unchanged).  ``--config 3`` times the trainer's per-step cost instead: one
@@ -23,11 +24,26 @@ starts ``python -m torch.distributed.run --nproc-per-node N bench.py ...`` as a
 child process -- the parent makes no GPU call -- forwards rank 0's JSON line and
 exits with the child's return code.
 
-Extra fields: the ranks the process group saw and their devices, eager
+A plain run sets up, warms up, times the K steps, writes the last timed step's
+outputs if ``--dump-outputs DIR`` is given, and prints the JSON line: the headline
+value, ``ms_per_step``, the ranks the process group saw and their devices, and the
+roofline record of the step kernel (HIP-event time of the timed region itself).
+
+``--full`` adds the legs that take runs of their own, after the timed region: eager
 (un-captured) throughput, the launch floor (an empty kernel in the step's launch
-shape replayed the same way), the roofline record of the step kernel (HIP-event
-timed), and the CPU baseline (the oracle's C restatement on a bounded sample of
-the same workload, timed on rank 0 after the timed region).
+shape replayed the same way), the fused bench mode, the isolated per-launch event
+pairs, the measured HBM traffic record, at N > 1 the strong-scaling region and the
+optional ``--gather`` leg, and the CPU baseline (the oracle's C restatement on a
+bounded sample of the same workload, timed on rank 0) beside the reference's own
+CPU figures.  Without it their fields are null.
+
+``--dump-outputs DIR``: what the caller of the timed path receives from its last
+timed step -- ``r_env`` (float64), ``r_shaped`` and ``done`` (float32; done is 0 / 1),
+config 3 also the four observation tensors (float32) -- as ``DIR/<name>.npy`` (ranks
+above 0: ``<name>.rank<r>.npy``).  Above 60 MB in all, a fixed sample of envs
+(RandomState(0), sorted; its indices in ``sample_env_index.npy``) is written instead.
+Inputs are the same from run to run (env seeds, Philox actions), so two builds can be
+compared output for output.
 """
 from __future__ import annotations
 
@@ -77,7 +93,7 @@ def parse(argv=None):
                     help="BASELINE.json config: 2 = map1 4096 envs per GPU (the headline), 3 = map1 16384 envs per "
                          "GPU with full observations every step, 4 = 65536 mixed-map envs over all ranks, "
                          "5 = 131072 synthetic 64x64 16-agent envs over all ranks")
-    ap.add_argument("--steps", type=int, default=2000)
+    ap.add_argument("--steps", type=int, default=2000, help="timed steps (exactly this many)")
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--envs", type=int, default=None, help="envs per GPU (default: 4096; config 3: 16384)")
     ap.add_argument("--total-envs", type=int, default=0,
@@ -88,7 +104,15 @@ def parse(argv=None):
     ap.add_argument("--T", type=int, default=None)
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--graph-steps", type=int, default=100)
-    ap.add_argument("--cpu-seconds", type=float, default=8.0, help="CPU baseline budget per leg (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the legs beside the headline: eager launches, launch "
+                         "floor, fused bench mode, isolated event pairs, measured-traffic record, CPU baseline, "
+                         "at N > 1 the strong-scaling region and --gather (default: the timed region only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64, at most "
+                         "60 MB: a fixed sample of envs beyond that)")
+    ap.add_argument("--cpu-seconds", type=float, default=8.0,
+                    help="--full: CPU baseline budget per leg (0 = skip)")
     ap.add_argument("--traffic-json", default=os.path.join(REPO, "profiles", "traffic.json"))
     ap.add_argument("--fused-k", type=int, default=100, help="bench mode (ii): steps per fused launch (0 = skip)")
     ap.add_argument("--no-floor", action="store_true", help="skip the launch-floor leg")
@@ -110,6 +134,10 @@ def parse(argv=None):
                     help="skip the eager, isolated-launch and floor legs (rocprof kernel-trace pass: the trace then "
                          "holds only the warmup and the timed graph replay, so its average is the timed region's)")
     a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.gather and not a.full:
+        ap.error("--gather is a --full leg: pass --full with it")
     c = CONFIGS[a.config]
     if a.map is not None and a.config not in ("2", "3"):
         ap.error("--map applies to configs 2 and 3 only")
@@ -321,6 +349,33 @@ def gather_leg(args, D, env, run0, dev, dist, world, reps=20):
                      "gloo: through host memory -- rehearsal of the code path only, not an xGMI figure")}
 
 
+DUMP_BYTES_CAP = 60 * 1000 * 1000   # all ranks' files together stay under 64 MB
+
+
+def dump_outputs(out_dir, rank, world, tensors):
+    """Write device tensors of leading dimension E (one row per local env) as
+    out_dir/<name>.npy (rank r > 0: <name>.rank<r>.npy): float64 stays, everything else becomes
+    float32.  If this rank's share of DUMP_BYTES_CAP does not hold all E rows, the same fixed
+    sample of rows (RandomState(0), sorted) of every tensor is written, with its indices (as
+    float64) in sample_env_index.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    E = next(iter(tensors.values())).shape[0]
+    as_dtype = {k: (torch.float64 if t.dtype is torch.float64 else torch.float32) for k, t in tensors.items()}
+    row_bytes = sum((t.numel() // E) * (8 if as_dtype[k] is torch.float64 else 4) for k, t in tensors.items())
+    n = min(E, max(1, (DUMP_BYTES_CAP // world) // (row_bytes + 8)))
+    idx = None
+    if n < E:
+        idx = np.sort(np.random.RandomState(0).choice(E, n, replace=False))
+        tensors = dict(tensors, sample_env_index=torch.from_numpy(idx.astype(np.float64)))
+        as_dtype["sample_env_index"] = torch.float64
+        sel = torch.from_numpy(idx)
+    suffix = "" if rank == 0 else f".rank{rank}"
+    for k, t in tensors.items():
+        if idx is not None and k != "sample_env_index":
+            t = t[sel.to(t.device)]
+        np.save(os.path.join(out_dir, f"{k}{suffix}.npy"), t.to(as_dtype[k]).cpu().numpy())
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     args = parse(argv)
@@ -377,8 +432,8 @@ def main(argv=None):
     env.reset()
 
     G = max(1, min(args.graph_steps, args.steps))
-    n_graph = (args.steps + G - 1) // G
-    K = n_graph * G
+    K = args.steps
+    n_graph, rem = divmod(K, G)   # K = n_graph replays of the G-step graph + one of a rem-step graph
     gen = torch.Generator(device=dev).manual_seed(0 + rank)
     acts = torch.randint(0, 15, (G, E, A), generator=gen, device=dev, dtype=torch.int32).to(torch.uint8)
     r = torch.zeros(E, dtype=torch.float64, device=dev)
@@ -412,20 +467,28 @@ def main(argv=None):
 
     def graph_region(fn):
         """K calls of fn(k): captured as a G-call hipGraph (torch's stream capture covers the
-        ctypes launches), replayed once untimed (the first launch of a fresh graph uploads it),
-        then W warmup calls as one replay of a W-call graph (launched the way the timed calls
-        are, right before the timed region), then barrier + the timed n_graph replays.
+        ctypes launches) and, where G does not divide K, a graph of the K mod G calls left over;
+        each replayed once untimed (the first launch of a fresh graph uploads it), then W warmup
+        calls as one replay of a W-call graph (launched the way the timed calls are, right before
+        the timed region), then barrier + the timed n_graph replays (+ the left-over graph's).
         Returns (max-over-ranks is applied by the caller) wall seconds and HIP-event ms."""
         side.wait_stream(torch.cuda.current_stream())
         g = torch.cuda.CUDAGraph()
+        g_rem = torch.cuda.CUDAGraph() if rem else None
         with torch.cuda.stream(side):
             fn(0)  # prime on the side stream
             torch.cuda.synchronize()
             with torch.cuda.graph(g, stream=side):
                 for k in range(G):
                     fn(k)
+            if rem:
+                with torch.cuda.graph(g_rem, stream=side):
+                    for k in range(rem):
+                        fn(k)
         torch.cuda.synchronize()
         g.replay()
+        if rem:
+            g_rem.replay()
         torch.cuda.synchronize()
         if args.warmup > 0:
             wg = torch.cuda.CUDAGraph()
@@ -445,6 +508,8 @@ def main(argv=None):
         t0 = time.perf_counter()
         for _ in range(n_graph):
             g.replay()
+        if rem:
+            g_rem.replay()
         e1.record()
         w = stop_clock(t0)
         return w, e0.elapsed_time(e1)
@@ -468,9 +533,17 @@ def main(argv=None):
     # the layout of the launches just timed, as the engine recorded it (step_obs: its fused wave kernel)
     layout = "wave" if obs_cfg else env.last_step_layout()
 
+    # ---- what the last timed step returned (before any later leg overwrites the buffers) ----
+    if args.dump_outputs:
+        outs = {"r_env": r, "r_shaped": sh, "done": dn}
+        if obs_cfg:
+            outs.update(obs_bufs)
+        dump_outputs(args.dump_outputs, rank, world, outs)
+
+    # ---- everything below the timed region is a --full leg ----
     # ---- eager throughput (same kernels, one ctypes launch per step) ----
     wall_eager = None
-    if not args.graph_only:
+    if args.full and not args.graph_only:
         barrier()
         t1 = time.perf_counter()
         for k in range(K):
@@ -480,12 +553,12 @@ def main(argv=None):
     # ---- launch floor: an empty kernel in mdl_step's launch shape (grid, workgroup, LDS,
     # kernel-argument layout), replayed exactly as the timed steps are ----
     wall_floor = gpu_ms_floor = None
-    if not obs_cfg and not args.no_graph and not args.graph_only and not args.no_floor:
+    if args.full and not obs_cfg and not args.no_graph and not args.graph_only and not args.no_floor:
         wall_floor, gpu_ms_floor = graph_region(lambda k: env.step_floor())
 
     # ---- bench mode: fused_k steps per launch, each env's
     # state in registers between steps; same action stream; not the API path ----
-    wall_f, nf, Kf = None, 0, (0 if obs_cfg else args.fused_k)
+    wall_f, nf, Kf = None, 0, (args.fused_k if args.full and not obs_cfg else 0)
     if Kf > 0:
         facts = acts.repeat((Kf + G - 1) // G, 1, 1)[:Kf].contiguous()
         fr = torch.empty((Kf, E), dtype=torch.float64, device=dev)
@@ -505,7 +578,7 @@ def main(argv=None):
     # plus an isolated per-launch event pair for reference ----
     kdur_us = gpu_ms / K * 1e3
     kdur_iso_us = None
-    if not args.graph_only:
+    if args.full and not args.graph_only:
         nk = min(K, 200)
         starts = [torch.cuda.Event(enable_timing=True) for _ in range(nk)]
         ends = [torch.cuda.Event(enable_timing=True) for _ in range(nk)]
@@ -528,7 +601,8 @@ def main(argv=None):
     # ---- N > 1, config 2: a second timed region on the metric's own workload -- 4,096 envs in
     # TOTAL split over the ranks (strong scaling; shard_strong, seeds 42 + global id)
     strong = None
-    if dist is not None and world > 1 and args.config == "2" and args.total_envs == 0 and not args.no_strong:
+    if args.full and dist is not None and world > 1 and args.config == "2" and args.total_envs == 0 \
+            and not args.no_strong:
         strong = strong_region(args, D, marl_gpu, grids[0], rank, world, dev, graph_region, obs_dims, G, K, dist)
 
     # ---- optional rollout collation (N > 1): one step of critic vectors all-gathered over the ranks
@@ -551,7 +625,7 @@ def main(argv=None):
         # the kernel the engine launched (its own record and symbol: no Python mirror of its rules)
         kname = env.step_kernel_name(layout, with_obs=obs_cfg) + (" (mixed maps)" if len(grids) > 1 else "")
         traffic, traffic_rec = None, None
-        if os.path.exists(args.traffic_json):
+        if args.full and os.path.exists(args.traffic_json):
             try:
                 tj = json.load(open(args.traffic_json))
                 want = {"envs": E, "agents": A, "packages": P, "maps": args.maps}
@@ -563,7 +637,8 @@ def main(argv=None):
             except (OSError, ValueError):
                 traffic = None
         cpu = cpu1 = None
-        if args.cpu_seconds > 0:   # after every rank's timed region (the others wait in the closing barrier)
+        # after every rank's timed region (the others wait in the closing barrier)
+        if args.full and args.cpu_seconds > 0:
             host = host_cpu_info()
             nt = host["threads_used"]
             m0, b0, n0 = runs[0]
@@ -595,7 +670,7 @@ def main(argv=None):
             "process_group_backend": None if dist is None else dist.get_backend(),
             "steps": K,
             "warmup": args.warmup,
-            "graph_upload_replay_steps": 0 if args.no_graph else G,
+            "graph_upload_replay_steps": 0 if args.no_graph else G + rem,
             "graph_steps": 0 if args.no_graph else G,
             "host_wait": args.host_wait if host_wait_rc in (None, 0) else f"{args.host_wait} (hipError {host_wait_rc})",
             "ms_per_step": ms_step,
@@ -636,7 +711,9 @@ def main(argv=None):
                         "actions (bit-exact with K mdl_step calls); not the API path, not the headline value"},
             "cpu_baseline": cpu,
             "cpu_baseline_1thread": cpu1,
-            "reference_cpu": REFERENCE_CPU,
+            "reference_cpu": REFERENCE_CPU if args.full else None,
+            "full": args.full,
+            "dumped_outputs": args.dump_outputs,
             "strong_4096": strong,
             "rollout_gather": gather,
         }

@@ -19,10 +19,10 @@ if [ -z "${SKIP_SUITE:-}" ]; then
   run pytest_gpu 1500 python -u -m pytest tests -m gpu -x -v -p no:cacheprovider --timeout 300 --timeout-method thread ${PYTEST_ARGS:-}
   run smoke 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')"
 fi
-run bench_driver 300 python bench.py --steps 20 --warmup 5
-run bench_long 300 python bench.py --cpu-seconds 0 --steps 2000 --warmup 200
-run bench_gpus2 300 python bench.py --gpus 2 --backend gloo --steps 40 --warmup 5 --cpu-seconds 2 --gather
-run bench_c3 300 python bench.py --config 3 --steps 200 --warmup 20 --cpu-seconds 4
-run bench_c4 300 python bench.py --config 4 --steps 200 --warmup 20 --cpu-seconds 2 --fused-k 0
-run bench_c5 300 python bench.py --config 5 --steps 200 --warmup 20 --cpu-seconds 2 --fused-k 0
+run bench_driver 300 python bench.py --full --steps 20 --warmup 5
+run bench_long 300 python bench.py --full --cpu-seconds 0 --steps 2000 --warmup 200
+run bench_gpus2 300 python bench.py --full --gpus 2 --backend gloo --steps 40 --warmup 5 --cpu-seconds 2 --gather
+run bench_c3 300 python bench.py --full --config 3 --steps 200 --warmup 20 --cpu-seconds 4
+run bench_c4 300 python bench.py --full --config 4 --steps 200 --warmup 20 --cpu-seconds 2 --fused-k 0
+run bench_c5 300 python bench.py --full --config 5 --steps 200 --warmup 20 --cpu-seconds 2 --fused-k 0
 exit 0

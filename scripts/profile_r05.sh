@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round-5 profile pass of the committed build (outputs under gpurun_out/prof_r05; scripts/collect_profiles_r05.py
 # copies the summaries and the per-dispatch PMC rows into profiles/r05/ and regenerates profiles/traffic.json):
-#   1. rocprofv3 kernel trace + stats of the driver's exact bench command (bench.py --steps 20 --warmup 5)
+#   1. rocprofv3 kernel trace + stats of the driver's exact bench command (bench.py --full --steps 20 --warmup 5)
 #   2. kernel trace + stats of the 2000-step graph-replayed config-2 bench (the timed region only)
 #   3. kernel trace + stats of bench.py --config 3 (fused step + observations) and --config 5
 #   4. PMC passes on eager launches, one counter set per pass: FETCH_SIZE, WRITE_SIZE, SQ -- config 2
@@ -21,7 +21,7 @@ pmc() {   # dir log counters... -- bench args
   timeout -s KILL 120 rocprofv3 --pmc $PMC --kernel-include-regex "$rx" -d $O/$d -o run --output-format csv -- python3 $R/bench.py "$@" > $O/$lg.log 2>&1
   local rc=$?; echo "pmc $d rc=$rc"; [ $rc -ne 0 ] && { tail -20 $O/$lg.log; exit $rc; }; return 0
 }
-run driver_bench 300 rocprofv3 --kernel-trace --stats -d $O/driver -o run --output-format csv -- python3 $R/bench.py --steps 20 --warmup 5
+run driver_bench 300 rocprofv3 --kernel-trace --stats -d $O/driver -o run --output-format csv -- python3 $R/bench.py --full --steps 20 --warmup 5
 run trace_bench 300 rocprofv3 --kernel-trace --stats -d $O/trace -o run --output-format csv -- python3 $R/bench.py --cpu-seconds 0 --graph-only --fused-k 0 --steps 2000 --warmup 20
 run c3_bench 300 rocprofv3 --kernel-trace --stats -d $O/c3trace -o run --output-format csv -- python3 $R/bench.py --config 3 --cpu-seconds 0 --graph-only --steps 300 --warmup 20
 run c4_bench 300 rocprofv3 --kernel-trace --stats -d $O/c4trace -o run --output-format csv -- python3 $R/bench.py --config 4 --cpu-seconds 0 --graph-only --fused-k 0 --steps 300 --warmup 20

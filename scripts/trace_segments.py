@@ -1,4 +1,4 @@
-"""Split a rocprofv3 kernel trace of bench.py into its phases (eager warmup,
+"""Split a rocprofv3 kernel trace of bench.py --full into its phases (eager warmup,
 graph replay, eager, isolated launches) and report per-phase kernel durations,
 so the rocprof average can be set beside bench.py's event-timed kernel_us.
 usage: trace_segments.py <run_kernel_trace.csv> <kernel-substring> <warmup> <steps>"""

@@ -17,7 +17,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def _run(extra, port):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(REPO, "bench.py"),
-           "--gpus", "2", "--steps", "40", "--warmup", "5", "--cpu-seconds", "0", "--fused-k", "0",
+           "--gpus", "2", "--full", "--steps", "40", "--warmup", "5", "--cpu-seconds", "0", "--fused-k", "0",
            "--backend", "gloo", "--envs", "512"] + extra
     env = dict(os.environ, OMP_NUM_THREADS="1")
     out = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=240)
@@ -72,10 +72,10 @@ def _plain(args, timeout=300):
 
 
 def test_bench_plain_command_two_gpus_self_launches():
-    """`python3 bench.py --gpus 2 --backend gloo --steps 40 --warmup 5` as a plain
+    """`python3 bench.py --gpus 2 --full --backend gloo --steps 40 --warmup 5` as a plain
     command starts torch.distributed.run itself; the line says how many ranks the process group saw,
     which devices they ran on, and carries the CPU baseline (timed on rank 0 after the timed region)."""
-    d = _plain(["--gpus", "2", "--backend", "gloo", "--steps", "40", "--warmup", "5", "--cpu-seconds", "1",
+    d = _plain(["--gpus", "2", "--full", "--backend", "gloo", "--steps", "40", "--warmup", "5", "--cpu-seconds", "1",
                 "--fused-k", "0", "--gather"])
     assert d["n_gpus"] == 2 and d["ranks_seen"] == 2 and d["launcher"] == "self"
     assert d["process_group_backend"] == "gloo"
@@ -105,13 +105,63 @@ def test_bench_plain_command_two_gpus_self_launches():
     assert d["config"]["step_layout"].startswith("wave")
 
 
+def _bench_in_process(argv, capsys):
+    """bench.main(argv) in this process (one rank, cuda:0) -> its JSON line."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(REPO, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    capsys.readouterr()
+    assert bench.main(argv) == 0
+    lines = [ln for ln in capsys.readouterr().out.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    return json.loads(lines[0])
+
+
+@pytest.mark.parametrize("config,extra", [("2", []), ("2", ["--no-graph"]), ("3", [])])
+def test_bench_plain_run_times_exactly_steps_and_dumps_last_outputs(config, extra, tmp_path, capsys, monkeypatch):
+    """A plain run (no --full): --steps is the number of timed steps even where the graph length does
+    not divide it (23 = 2 x 10 + 3), the legs beside the headline are off, and --dump-outputs writes
+    the last timed step's outputs as float32 / float64 arrays, the same from run to run."""
+    import numpy as np
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "TORCHELASTIC_RUN_ID"):
+        monkeypatch.delenv(k, raising=False)
+    E, A = 300, 5
+    got = []
+    for d in ("a", "b"):
+        line = _bench_in_process(["--gpus", "1", "--config", config, "--envs", str(E), "--steps", "23", "--warmup", "3",
+                                  "--graph-steps", "10", "--dump-outputs", str(tmp_path / d)] + extra, capsys)
+        assert line["steps"] == 23 and line["full"] is False and line["ms_per_step"] > 0
+        assert line["value"] == pytest.approx(E * A * 23 / (line["ms_per_step"] * 23 / 1e3), rel=1e-9)
+        assert line["unit"] == "agent-steps/s" and line["higher_is_better"] is True and line["dtype"].startswith("int32+fp64")
+        for k in ("eager", "launch_floor", "fused_bench_mode", "cpu_baseline", "cpu_baseline_1thread", "reference_cpu",
+                  "strong_4096", "rollout_gather"):
+            assert line[k] is None, k
+        assert line["roofline"]["kernel_us_isolated_event_pair"] is None and line["roofline"]["traffic"] is None
+        got.append({f[:-4]: np.load(tmp_path / d / f) for f in os.listdir(tmp_path / d)})
+    a, b = got
+    want = {"r_env": ((E,), np.float64), "r_shaped": ((E,), np.float32), "done": ((E,), np.float32)}
+    if config == "3":
+        want.update(actor_map=((E, A, 6, 10, 10), np.float32), actor_vec=((E, A, 52), np.float32),
+                    critic_map=((E, 4, 10, 10), np.float32), critic_vec=((E, 1301), np.float32))
+    assert sorted(a) == sorted(b) == sorted(want)
+    for k, (shape, dt) in want.items():
+        assert a[k].shape == shape and a[k].dtype == dt, k
+        np.testing.assert_array_equal(a[k], b[k])
+    # a live step, not the zero-filled buffers the bench starts with
+    assert np.count_nonzero(a["r_shaped"]) > 0 and set(np.unique(a["done"])) <= {0.0, 1.0}
+    if config == "3":
+        assert np.count_nonzero(a["actor_map"]) > 0 and np.count_nonzero(a["critic_vec"]) > 0
+
+
 def test_bench_one_gpu_launch_floor_and_config3_leg():
-    """The default line carries the launch floor; `--config 3` times mdl_step_obs (step + full
+    """The `--full` line carries the launch floor; `--config 3` times mdl_step_obs (step + full
     observations) with the write-bytes roofline and the CPU leg that builds the same observations."""
-    d = _plain(["--steps", "40", "--warmup", "5", "--cpu-seconds", "0", "--fused-k", "0"])
+    d = _plain(["--full", "--steps", "40", "--warmup", "5", "--cpu-seconds", "0", "--fused-k", "0"])
     assert d["ranks_seen"] == 1 and d["launcher"] == "none" and d["launch_floor"]["ms_per_step"] > 0
     assert d["launch_floor_ms_per_step"] < d["ms_per_step"]
-    d3 = _plain(["--config", "3", "--envs", "2048", "--steps", "20", "--warmup", "5", "--cpu-seconds", "0.5"])
+    d3 = _plain(["--full", "--config", "3", "--envs", "2048", "--steps", "20", "--warmup", "5",
+                 "--cpu-seconds", "0.5"])
     assert d3["config"]["obs_dims"] == {"actor_vec": 52, "critic_vec": 1301, "obs_bytes_per_env_step": 19844}
     assert d3["roofline"]["algorithmic_bytes_per_env_step"] == 19844 + 586
     assert d3["roofline"]["kernel"] == "mdl::k_step_obs<true, 5>" and d3["launch_floor"] is None

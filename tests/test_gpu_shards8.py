@@ -98,7 +98,7 @@ def test_bench_torchrun_rccl_one_rank():
     all_reduce MAX of the per-rank clocks) under the driver's launcher, one rank on the one GPU."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", "29571", os.path.join(REPO, "bench.py"),
-           "--gpus", "1", "--backend", "nccl", "--steps", "40", "--warmup", "5", "--cpu-seconds", "0"]
+           "--gpus", "1", "--full", "--backend", "nccl", "--steps", "40", "--warmup", "5", "--cpu-seconds", "0"]
     env = dict(os.environ, OMP_NUM_THREADS="1")
     out = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=240)
     assert out.returncode == 0, out.stderr[-3000:]

@@ -322,6 +322,51 @@ def test_bench_step_layout_flag():
         bench.parse(["--step-layout", "diagonal"])
 
 
+def test_bench_full_and_dump_flags():
+    """A plain run is the timed region only: --full (off by default) switches the other legs on,
+    --gather is one of them, --steps counts timed steps (>= 1)."""
+    bench = _bench_module()
+    a = bench.parse(["--steps", "20", "--warmup", "5"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 20
+    a = bench.parse(["--full", "--gather", "--dump-outputs", "d"])
+    assert a.full is True and a.gather is True and a.dump_outputs == "d"
+    for bad in (["--gather"], ["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse(bad)
+
+
+def test_bench_dump_outputs_dtypes_and_sample(tmp_path, monkeypatch):
+    """--dump-outputs' writer: float64 stays, the rest becomes float32; under the byte cap every
+    row is written, above it the same seeded sample of rows of every tensor, indices beside it;
+    ranks above 0 write under their own names."""
+    import numpy as np
+    import torch
+    bench = _bench_module()
+    E = 37
+    t = {"r_env": torch.arange(E, dtype=torch.float64) * 0.25,
+         "done": (torch.arange(E) % 3 == 0).to(torch.uint8),
+         "actor_vec": torch.arange(E * 2 * 5, dtype=torch.float32).reshape(E, 2, 5)}
+    bench.dump_outputs(str(tmp_path / "all"), 0, 1, t)
+    got = {f[:-4]: np.load(tmp_path / "all" / f) for f in os.listdir(tmp_path / "all")}
+    assert sorted(got) == ["actor_vec", "done", "r_env"]
+    assert got["r_env"].dtype == np.float64 and got["done"].dtype == np.float32 and got["actor_vec"].dtype == np.float32
+    for k in t:
+        np.testing.assert_array_equal(got[k], t[k].numpy().astype(got[k].dtype))
+    row = 8 + 4 + 40 + 8   # bytes per env as written, plus its index
+    monkeypatch.setattr(bench, "DUMP_BYTES_CAP", 2 * 10 * row)   # two ranks, ten rows each
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), 1, 2, t)
+    s1 = {f: np.load(tmp_path / "s1" / f) for f in sorted(os.listdir(tmp_path / "s1"))}
+    assert sorted(s1) == [f"{k}.rank1.npy" for k in ("actor_vec", "done", "r_env", "sample_env_index")]
+    idx = s1["sample_env_index.rank1.npy"]
+    assert idx.dtype == np.float64 and len(idx) == 10 and len(set(idx)) == 10 and list(idx) == sorted(idx)
+    np.testing.assert_array_equal(s1["actor_vec.rank1.npy"], t["actor_vec"].numpy()[idx.astype(int)])
+    np.testing.assert_array_equal(s1["r_env.rank1.npy"], t["r_env"].numpy()[idx.astype(int)])
+    assert sum(a.nbytes for a in s1.values()) <= 10 * row
+    for f, a in s1.items():
+        np.testing.assert_array_equal(a, np.load(tmp_path / "s2" / f))
+
+
 _PROFILING_SWITCHES = ["MDL_EXP_NOWAIT", "MDL_EXP_NOTUPLES", "MDL_EXP_NOLDS", "MDL_ABLATE=1", "MDL_STAMPS"]
 
 
