@@ -39,6 +39,10 @@ constexpr int WAVE = 64;
 constexpr int MT_N = 624;
 constexpr int MT_M = 397;
 constexpr int MAX_MAPS = 8;
+// Elements of padding the engine allocates after the package table, the state words and the
+// tracker: the multi-env step kernels (k_step_rows, k_step_halves) load every lane's slots past
+// an env's P without clamping, at offsets their static_asserts keep below this.
+constexpr int PKG_PAD = 256;
 
 enum : int { ST_NONE = 0, ST_WAITING = 1, ST_IN_TRANSIT = 2, ST_DELIVERED = 3 };
 enum : int { MV_S = 0, MV_L = 1, MV_R = 2, MV_U = 3, MV_D = 4, MV_OTHER = 5 };

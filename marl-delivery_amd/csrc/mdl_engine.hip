@@ -109,9 +109,6 @@ int waves_per_block(size_t lds_per_wave) {
     return (int)w;
 }
 
-// elements of padding after the package table, state words and tracker (see mdl_create)
-constexpr size_t PKG_PAD = 256;
-
 }  // namespace
 
 struct MdlEngine {
@@ -148,8 +145,15 @@ struct MdlEngine {
         if (halves_for(n)) return MDL_STEP_LAYOUT_HALVES;
         return MDL_STEP_LAYOUT_WAVE;
     }
-    size_t lds_for(int32_t layout) const {
-        return layout == MDL_STEP_LAYOUT_ROWS ? lds_rows : layout == MDL_STEP_LAYOUT_HALVES ? lds_halves : lds_step;
+    // a step launch of `layout` over n envs: the per-wave LDS slice, waves per workgroup, envs per wave
+    struct StepShape {
+        size_t lds;
+        int wpb, epw;
+    };
+    StepShape step_shape(int32_t layout, int n) const {
+        const bool rows = layout == MDL_STEP_LAYOUT_ROWS, halves = layout == MDL_STEP_LAYOUT_HALVES;
+        const size_t lds = rows ? lds_rows : halves ? lds_halves : lds_step;
+        return {lds, step_wpb(n, n_cu, lds, p.P), rows ? 4 : halves ? 2 : 1};
     }
     int32_t last_step_layout = 0;   // MDL_STEP_LAYOUT_* of the last mdl_step launch (0: none yet)
     // A synchronous host-mapped call whose wait timed out leaves its launch queued on `hung`: until that
@@ -407,14 +411,14 @@ int mdl_create(const MdlConfig* cfg, const uint8_t* grids, const int32_t* map_hw
     rc |= eng->alloc(&d_recip, recip.size());
     if (env_map) rc |= eng->alloc(&d_em, E);
     rc |= eng->alloc(&p.rob, E * A);
-    // the package buffers end in 256 slots of padding: the multi-env step kernels load every lane's
-    // slot past an env's P without clamping (k_step_halves: up to the last env's slot 127)
-    rc |= eng->alloc(&p.pkg, E * P + PKG_PAD);
-    rc |= eng->alloc(&p.pstate, E * P + PKG_PAD);
+    // the package buffers end in PKG_PAD slots of padding (mdl_device.hpp): the multi-env step kernels
+    // load every lane's slot past an env's P without clamping (k_step_halves: up to the last env's slot 127)
+    rc |= eng->alloc(&p.pkg, E * P + mdl::PKG_PAD);
+    rc |= eng->alloc(&p.pstate, E * P + mdl::PKG_PAD);
     rc |= eng->alloc(&p.es, E);
     rc |= eng->alloc(&p.mt, E * mdl::MT_N);
     rc |= eng->alloc(&p.mt_pos, E);
-    rc |= eng->alloc(&p.trk, (p.stale ? E : 1) * P + PKG_PAD);
+    rc |= eng->alloc(&p.trk, (p.stale ? E : 1) * P + mdl::PKG_PAD);
     rc |= eng->alloc(&p.ep_total, E);
     rc |= eng->alloc(&p.ep_len, E);
     if (rc) {
@@ -576,20 +580,9 @@ int mdl_step(MdlEngine* eng, const uint8_t* actions, int32_t action_format, cons
     DeviceGuard dg(eng->device);
     const int32_t layout = eng->layout_for(n, env_ids != nullptr);
     eng->last_step_layout = layout;
-    if (layout == MDL_STEP_LAYOUT_ROWS) {
-        HIPCHK(mdl::launch_step_rows(eng->p, actions, action_format, n, auto_reset, r_env, r_shaped, done,
-                                     step_wpb(n, eng->n_cu, eng->lds_rows, eng->p.P), eng->lds_rows,
-                                     (hipStream_t)stream));
-        return 0;
-    }
-    if (layout == MDL_STEP_LAYOUT_HALVES) {
-        HIPCHK(mdl::launch_step_halves(eng->p, actions, action_format, n, auto_reset, r_env, r_shaped, done,
-                                       step_wpb(n, eng->n_cu, eng->lds_halves, eng->p.P), eng->lds_halves,
-                                       (hipStream_t)stream));
-        return 0;
-    }
-    HIPCHK(mdl::launch_step(eng->p, actions, action_format, env_ids, n, auto_reset, r_env, r_shaped, done,
-                            step_wpb(n, eng->n_cu, eng->lds_step, eng->p.P), eng->lds_step, (hipStream_t)stream));
+    const auto sh = eng->step_shape(layout, n);
+    HIPCHK(mdl::launch_step(eng->p, actions, action_format, env_ids, n, auto_reset, r_env, r_shaped, done, sh.wpb,
+                            sh.lds, (hipStream_t)stream, sh.epw));
     return 0;
 }
 
@@ -598,10 +591,8 @@ int mdl_step_floor(MdlEngine* eng, int32_t n, void* stream) {
     if (n < 1 || n > eng->p.E) return fail("mdl_step_floor: n=%d out of range", n);
     DeviceGuard dg(eng->device);
     // the launch shape of a full-batch mdl_step over n envs (the layout mdl_step takes for it)
-    const int32_t layout = eng->layout_for(n, false);
-    const size_t lds = eng->lds_for(layout);
-    const int epw = layout == MDL_STEP_LAYOUT_ROWS ? 4 : layout == MDL_STEP_LAYOUT_HALVES ? 2 : 1;
-    HIPCHK(mdl::launch_step_floor(eng->p, n, step_wpb(n, eng->n_cu, lds, eng->p.P), lds, (hipStream_t)stream, epw));
+    const auto sh = eng->step_shape(eng->layout_for(n, false), n);
+    HIPCHK(mdl::launch_step_floor(eng->p, n, sh.wpb, sh.lds, (hipStream_t)stream, sh.epw));
     return 0;
 }
 
@@ -627,8 +618,9 @@ int mdl_step_obs(MdlEngine* eng, const uint8_t* actions, int32_t action_format, 
             return 0;
         }
     }
-    HIPCHK(mdl::launch_step(eng->p, actions, action_format, nullptr, E, auto_reset, r_env, r_shaped, done,
-                            step_wpb(E, eng->n_cu, eng->lds_step, eng->p.P), eng->lds_step, s));
+    const auto sh = eng->step_shape(MDL_STEP_LAYOUT_WAVE, E);
+    HIPCHK(mdl::launch_step(eng->p, actions, action_format, nullptr, E, auto_reset, r_env, r_shaped, done, sh.wpb,
+                            sh.lds, s));
     HIPCHK(eng->launch_obs(0, E, actor_map, actor_vec, critic_map, critic_vec, s));
     return 0;
 }
@@ -644,8 +636,9 @@ int mdl_step_fused(MdlEngine* eng, const uint8_t* actions, int32_t action_format
     if (k_steps < 1) return fail("mdl_step_fused: k_steps=%d must be >= 1", k_steps);
     if (n == 0) return 0;
     DeviceGuard dg(eng->device);
+    const auto sh = eng->step_shape(MDL_STEP_LAYOUT_WAVE, n);
     HIPCHK(mdl::launch_step_fused(eng->p, actions, action_format, env_ids, n, k_steps, auto_reset, r_env, r_shaped,
-                                  done, step_wpb(n, eng->n_cu, eng->lds_step, eng->p.P), eng->lds_step, (hipStream_t)stream));
+                                  done, sh.wpb, sh.lds, (hipStream_t)stream));
     return 0;
 }
 
@@ -774,9 +767,9 @@ int mdl_mail_step(MdlEngine* eng, int32_t n, int32_t use_ids, int32_t auto_reset
     // one launch: the step, its rows into the mailbox, the completion word (k_step_mail)
     const int32_t want = eng->mail_seq = (eng->mail_seq % 0x7ffffff0) + 1;
     const mdl::MailRows rows{m.seq, m.robots, m.pkgs, m.t, m.total_reward, m.rterms};
+    const auto sh = eng->step_shape(MDL_STEP_LAYOUT_WAVE, n);
     HIPCHK(mdl::launch_step_mail(eng->p, m.codes, use_ids ? m.ids : nullptr, n, auto_reset, m.r_env, m.r_shaped,
-                                 m.done, step_wpb(n, eng->n_cu, eng->lds_step, eng->p.P), eng->lds_step, rows,
-                                 eng->mail_ctr, eng->mail_waves, want, s));
+                                 m.done, sh.wpb, sh.lds, rows, eng->mail_ctr, eng->mail_waves, want, s));
     eng->mail_waves += (unsigned)n;   // the n waves of rows [0, n) counted themselves
     return spin_wait(eng, m.seq, want, s, "mdl_mail_step");
 }
@@ -1255,8 +1248,7 @@ int mdl_step_kernel_name(const MdlEngine* eng, int32_t layout, int32_t with_obs,
     // mdl_step_obs's one-launch form (else it is mdl_step's wave kernel + the builder)
     const bool obs = with_obs && eng->p.obs_small && eng->p.A <= 8 && eng->p.P <= 64 &&
                      std::max(eng->lds_step, eng->lds_obs) <= LDS_BUDGET;
-    const int epw = layout == MDL_STEP_LAYOUT_ROWS ? 4 : layout == MDL_STEP_LAYOUT_HALVES ? 2 : 1;
-    const int k = mdl::step_kernel_name(eng->p, epw, obs, out, cap);
+    const int k = mdl::step_kernel_name(eng->p, eng->step_shape(layout, eng->p.E).epw, obs, out, cap);
     if (k < 0 || k >= cap) return fail("mdl_step_kernel_name: buffer of %d bytes too small", cap);
     return 0;
 }

@@ -22,7 +22,7 @@ struct FeatDims {
     int A, NS, HW, MPc, MPsc, stage;  // stage: floats of the vector staging slice
 };
 
-__host__ __device__ inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+__host__ __device__ constexpr size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 __host__ __device__ inline size_t feat_lds_bytes(const FeatDims& d) {
     size_t s = 0;

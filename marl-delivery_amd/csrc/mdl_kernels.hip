@@ -18,6 +18,7 @@
 // lane j%64 of chunk j/64 (NCH chunks, compile-time).  Cross-lane work is
 // readlane / ballot only; LDS is touched only when an env resets.
 #include <cstring>
+#include <type_traits>
 
 #include "mdl_kernels.hpp"
 #include "mdl_features.hpp"
@@ -60,7 +61,7 @@ struct ResetLds {
     uint8_t* pst;       // [P]
 };
 
-__host__ __device__ inline size_t reset_lds_bytes(int P) {
+__host__ __device__ constexpr size_t reset_lds_bytes(int P) {
     return align16(8 * (size_t)P) * 2 + align16(4 * MT_N) + align16(2 * 64) + align16((size_t)P);
 }
 
@@ -1763,46 +1764,9 @@ hipError_t launch_tracker_clear(const DevParams& p, const int* ids, int n, hipSt
     return hipGetLastError();
 }
 
-template <bool ST, int NCH, bool FUSED>
-static void launch_step_t(const DevParams& p, const uint8_t* actions, int fmt, const int* ids, int n, int auto_reset,
-                          double* r, float* sh, uint8_t* done, int wpb, size_t lds, int K, hipStream_t s) {
-    // n and wpb travel packed in one preloaded dword (n < 2^24, wpb < 32; the engine
-    // checks both at creation)
-    const int threads = 64 * wpb;
-#ifdef MDL_EXP_NOLDS  // profiling builds only: no LDS request (valid only while no env resets)
-    lds = 0;
-#endif
-    StepArgs a;
-    a.p = p;
-    a.actions = actions;
-    a.env_ids = ids;
-    a.r_out = r;
-    a.sh_out = sh;
-    a.done_out = done;
-    a.fmt = fmt;
-    a.n = n;
-    a.auto_reset = auto_reset;
-    a.wpb = wpb;
-    a.lds_stride = (int)lds;
-    a.K = K;
-    const dim3 grid(blocks_for(n, wpb)), block(threads);
-    const uint32_t ap = pack_ap(p.A, p.P, (int)grid.x);
-    const uint32_t nw = (uint32_t)n | ((uint32_t)wpb << 24) | (ids ? NW_IDS : 0u) | (p.env_map ? NW_MAP : 0u);
-#define MDL_STEP_ARGS p.rob, p.pkg, p.pstate, (const u32x4*)p.es, p.trk, actions, ap, nw, a
-    if (NCH <= 2 && p.A == 5)
-        hipLaunchKernelGGL((k_step<ST, NCH, FUSED, (NCH <= 2 ? 5 : 8)>), grid, block, lds * wpb, s, MDL_STEP_ARGS);
-    else if (NCH <= 2 && p.A == 16)   // config 5's robot count
-        hipLaunchKernelGGL((k_step<ST, NCH, FUSED, (NCH <= 2 ? 16 : 8)>), grid, block, lds * wpb, s, MDL_STEP_ARGS);
-    else if (p.A <= 8)
-        hipLaunchKernelGGL((k_step<ST, NCH, FUSED, 8>), grid, block, lds * wpb, s, MDL_STEP_ARGS);
-    else
-        hipLaunchKernelGGL((k_step<ST, NCH, FUSED, 0>), grid, block, lds * wpb, s, MDL_STEP_ARGS);
-#undef MDL_STEP_ARGS
-}
-
 // P <= 64 (four chunks per lane).  Eight chunks (P <= 128) were built and measured slower than
 // k_step at P = 100 (16,384 envs 14.2 vs 10.6 us, 65,536 39.7 vs 33.9: profiles/r05/rows_ab.txt)
-bool step_rows_ok(int A, int P) { return A >= 1 && A <= 8 && P >= 1 && P <= ROW * 4; }
+bool step_rows_ok(int A, int P) { return A >= 1 && A <= 8 && P >= 1 && P <= ROWS_MAX_P; }
 size_t step_rows_lds(int P) {
     const size_t a = reset_lds_bytes(P), b = rows_scratch_bytes(4);
     return a > b ? a : b;
@@ -1810,169 +1774,156 @@ size_t step_rows_lds(int P) {
 
 // A == 16 exactly (numpy's pairwise sum of 16 values in-row; 9..15 would need its sequential
 // tail), P <= 128 (four 32-lane chunks)
-bool step_halves_ok(int A, int P) { return A == 16 && P >= 1 && P <= HALF * HALF_NC; }
+bool step_halves_ok(int A, int P) { return A == 16 && P >= 1 && P <= HALVES_MAX_P; }
 size_t step_halves_lds(int P) {
     const size_t a = reset_lds_bytes(P), b = halves_scratch_bytes();
     return a > b ? a : b;
 }
 
-hipError_t launch_step_halves(const DevParams& p, const uint8_t* actions, int fmt, int n, int auto_reset, double* r,
-                              float* sh, uint8_t* done, int wpb, size_t lds, hipStream_t s) {
-    if (!step_halves_ok(p.A, p.P)) return hipErrorInvalidValue;
-    StepArgs a;
-    a.p = p;
-    a.actions = actions;
-    a.env_ids = nullptr;
-    a.r_out = r;
-    a.sh_out = sh;
-    a.done_out = done;
-    a.fmt = fmt;
-    a.n = n;
-    a.auto_reset = auto_reset;
-    a.wpb = wpb;
-    a.lds_stride = (int)lds;
-    a.K = 1;
-    const int waves = (n + 1) / 2;
-    const dim3 grid(blocks_for(waves, wpb)), block(64 * wpb);
-    const uint32_t ap = pack_ap(p.A, p.P, (int)grid.x);
-    bool small = true;
-    for (int k = 0; k < p.n_maps; k++) small = small && p.maps[k].H <= 64 && p.maps[k].W <= 64;
-    const uint32_t nw = (uint32_t)n | ((uint32_t)wpb << 24) | (p.env_map ? NW_MAP : 0u) | (small ? NW_SMALLMAP : 0u);
-#define MDL_STEP_ARGS p.rob, p.pkg, p.pstate, (const u32x4*)p.es, p.trk, actions, ap, nw, a
-    const bool full3 = p.P >= 3 * HALF;
-    if (p.stale && full3) hipLaunchKernelGGL((k_step_halves<true, 3>), grid, block, lds * wpb, s, MDL_STEP_ARGS);
-    else if (p.stale) hipLaunchKernelGGL((k_step_halves<true, 0>), grid, block, lds * wpb, s, MDL_STEP_ARGS);
-    else if (full3) hipLaunchKernelGGL((k_step_halves<false, 3>), grid, block, lds * wpb, s, MDL_STEP_ARGS);
-    else hipLaunchKernelGGL((k_step_halves<false, 0>), grid, block, lds * wpb, s, MDL_STEP_ARGS);
-#undef MDL_STEP_ARGS
-    return hipGetLastError();
+// ---- the step launches: one kernel selection (select_step), one argument path (step_launch) ----
+// STEP_PLAIN: k_step, k_step_halves or k_step_rows by envs per wave (1, 2, 4); the others: one wave per env
+enum StepVariant { STEP_PLAIN, STEP_FUSED, STEP_OBS, STEP_MAIL };
+
+// f(std::integral_constant<int, V>{}) for the V of Vs... that equals v
+template <int... Vs, class F>
+static void with_int(int v, F&& f) {
+    (void)((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
 }
 
-hipError_t launch_step_rows(const DevParams& p, const uint8_t* actions, int fmt, int n, int auto_reset, double* r,
-                            float* sh, uint8_t* done, int wpb, size_t lds, hipStream_t s) {
-    if (!step_rows_ok(p.A, p.P)) return hipErrorInvalidValue;
-    StepArgs a;
-    a.p = p;
-    a.actions = actions;
-    a.env_ids = nullptr;
-    a.r_out = r;
-    a.sh_out = sh;
-    a.done_out = done;
-    a.fmt = fmt;
-    a.n = n;
-    a.auto_reset = auto_reset;
-    a.wpb = wpb;
-    a.lds_stride = (int)lds;
-    a.K = 1;
-    const int waves = (n + 3) / 4;
-    const dim3 grid(blocks_for(waves, wpb)), block(64 * wpb);
-    const uint32_t ap = pack_ap(p.A, p.P, (int)grid.x);
-    const uint32_t nw = (uint32_t)n | ((uint32_t)wpb << 24) | (p.env_map ? NW_MAP : 0u);
-#define MDL_STEP_ARGS p.rob, p.pkg, p.pstate, (const u32x4*)p.es, p.trk, actions, ap, nw, a
-#define MDL_ROWS(ST, NF)                                                                                     \
-    do {                                                                                                     \
-        if (p.A == 5) hipLaunchKernelGGL((k_step_rows<ST, 5, 4, NF>), grid, block, lds * wpb, s, MDL_STEP_ARGS);   \
-        else hipLaunchKernelGGL((k_step_rows<ST, 8, 4, NF>), grid, block, lds * wpb, s, MDL_STEP_ARGS);      \
-    } while (0)
-    const bool full3 = p.P >= 3 * ROW;
-    if (p.stale && full3) MDL_ROWS(true, 3);
-    else if (p.stale) MDL_ROWS(true, 0);
-    else if (full3) MDL_ROWS(false, 3);
-    else MDL_ROWS(false, 0);
-#undef MDL_ROWS
-#undef MDL_STEP_ARGS
-    return hipGetLastError();
+// The step kernel a launch of variant V over `envs_per_wave` envs per wavefront runs: calls
+// f(kernel, fmt, args...) with the instantiation and its symbol as rocprof names it -- a printf
+// format and its arguments, the template arguments chosen here (a launch never prints it).
+// Every rule of the dispatch lives here and nowhere else.
+template <StepVariant V, class F>
+static void select_step(const DevParams& p, int envs_per_wave, F&& f) {
+    const int A = p.A, P = p.P, nch = nch_for(P);
+    with_int<0, 1>(p.stale != 0, [&](auto st) {
+        constexpr bool ST = decltype(st)::value != 0;
+        auto hit = [&](auto kernel, const char* fmt, auto... targs) { f(kernel, fmt, ST ? "true" : "false", targs...); };
+        if constexpr (V == STEP_OBS) {   // NCH = 1, A <= 8 (launch_step_obs refuses the rest)
+            with_int<5, 8>(A == 5 ? 5 : 8, [&](auto au) {
+                constexpr int AU = decltype(au)::value;
+                hit(k_step_obs<ST, AU>, "mdl::k_step_obs<%s, %d>", AU);
+            });
+        } else if constexpr (V == STEP_MAIL) {
+            with_int<1, 2, 4, 8, 16>(nch, [&](auto nc) {
+                with_int<8, 0>(A <= 8 ? 8 : 0, [&](auto au) {
+                    constexpr int NCH = decltype(nc)::value, AU = decltype(au)::value;
+                    hit(k_step_mail<ST, NCH, AU>, "mdl::k_step_mail<%s, %d, %d>", NCH, AU);
+                });
+            });
+        } else if (V == STEP_PLAIN && envs_per_wave == 4) {
+            with_int<5, 8>(A == 5 ? 5 : 8, [&](auto au) {
+                with_int<0, 3>(P >= 3 * ROW ? 3 : 0, [&](auto nf) {
+                    constexpr int AU = decltype(au)::value, NF = decltype(nf)::value;
+                    hit(k_step_rows<ST, AU, 4, NF>, "mdl::k_step_rows<%s, %d, 4, %d>", AU, NF);
+                });
+            });
+        } else if (V == STEP_PLAIN && envs_per_wave == 2) {
+            with_int<0, 3>(P >= 3 * HALF ? 3 : 0, [&](auto nf) {
+                constexpr int NF = decltype(nf)::value;
+                hit(k_step_halves<ST, NF>, "mdl::k_step_halves<%s, %d>", NF);
+            });
+        } else {
+            with_int<1, 2, 4, 8, 16>(nch, [&](auto nc) {
+                constexpr int NCH = decltype(nc)::value;
+                constexpr bool FUSED = V == STEP_FUSED;
+                auto leaf = [&](auto au) {
+                    constexpr int AU = decltype(au)::value;
+                    hit(k_step<ST, NCH, FUSED, AU>,
+                        FUSED ? "mdl::k_step<%s, %d, true, %d>" : "mdl::k_step<%s, %d, false, %d>", NCH, AU);
+                };
+                // the exact-A forms (the configs' 5, and 16: config 5's robot count) only up to two chunks
+                const int au = (NCH <= 2 && A == 5) ? 5 : (NCH <= 2 && A == 16) ? 16 : A <= 8 ? 8 : 0;
+                if constexpr (NCH <= 2) with_int<5, 16, 8, 0>(au, leaf);
+                else with_int<8, 0>(au, leaf);
+            });
+        }
+    });
 }
 
-// (the dispatch of launch_step_rows / launch_step_halves above, launch_step_obs and launch_step_t below)
 int step_kernel_name(const DevParams& p, int envs_per_wave, bool obs, char* out, int cap) {
-    const char* st = p.stale ? "true" : "false";
-    if (envs_per_wave == 4)
-        return snprintf(out, (size_t)cap, "mdl::k_step_rows<%s, %d, 4, %d>", st, p.A == 5 ? 5 : 8, p.P >= 3 * ROW ? 3 : 0);
-    if (envs_per_wave == 2) return snprintf(out, (size_t)cap, "mdl::k_step_halves<%s, %d>", st, p.P >= 3 * HALF ? 3 : 0);
-    if (obs) return snprintf(out, (size_t)cap, "mdl::k_step_obs<%s, %d>", st, p.A == 5 ? 5 : 8);
-    const int nch = nch_for(p.P);
-    const int au = (nch <= 2 && p.A == 5) ? 5 : (nch <= 2 && p.A == 16) ? 16 : p.A <= 8 ? 8 : 0;
-    return snprintf(out, (size_t)cap, "mdl::k_step<%s, %d, false, %d>", st, nch, au);
+    int k = -1;
+    auto put = [&](auto, const char* fmt, auto... targs) { k = snprintf(out, (size_t)cap, fmt, targs...); };
+    if (obs) select_step<STEP_OBS>(p, 1, put);
+    else select_step<STEP_PLAIN>(p, envs_per_wave, put);
+    return k;
+}
+
+// One step launch's shape and kernel arguments (every step kernel starts with StepKarg's fields);
+// operator() launches `kernel` with them, a variant's own arguments (ObsArgs; MailArgs, inl) behind.
+struct StepLaunch {
+    StepArgs a;
+    dim3 grid, block;
+    size_t dyn;
+    uint32_t ap, nw;
+    template <class Kernel, class... Extra>
+    void operator()(Kernel kernel, hipStream_t s, const Extra&... extra) const {
+        const DevParams& p = a.p;
+        hipLaunchKernelGGL(kernel, grid, block, dyn, s, p.rob, p.pkg, p.pstate, (const u32x4*)p.es, p.trk, a.actions,
+                           ap, nw, a, extra...);
+    }
+};
+
+// n and wpb travel packed in one preloaded dword (n < 2^24, wpb < 32; the engine checks both at
+// creation), with the flags: NW_IDS with an id list, NW_MAP with per-env maps, NW_SMALLMAP for
+// k_step_halves when every map is at most 64 x 64
+static StepLaunch step_launch(const DevParams& p, const uint8_t* actions, int fmt, const int* ids, int n,
+                              int auto_reset, double* r, float* sh, uint8_t* done, int wpb, size_t lds, int K,
+                              int envs_per_wave) {
+    const dim3 grid(blocks_for((n + envs_per_wave - 1) / envs_per_wave, wpb));
+    bool small = envs_per_wave == 2;
+    for (int k = 0; k < p.n_maps; k++) small = small && p.maps[k].H <= 64 && p.maps[k].W <= 64;
+    const uint32_t nw = (uint32_t)n | ((uint32_t)wpb << 24) | (ids ? NW_IDS : 0u) | (p.env_map ? NW_MAP : 0u) |
+                        (small ? NW_SMALLMAP : 0u);
+    return StepLaunch{StepArgs{p, actions, ids, r, sh, done, fmt, n, auto_reset, wpb, (int)lds, K},
+                      grid, dim3(64 * wpb), lds * wpb, pack_ap(p.A, p.P, (int)grid.x), nw};
+}
+
+template <StepVariant V>
+static hipError_t launch_step_v(const DevParams& p, const uint8_t* actions, int fmt, const int* ids, int n,
+                                int auto_reset, double* r, float* sh, uint8_t* done, int wpb, size_t lds, int K,
+                                int envs_per_wave, hipStream_t s) {
+#ifdef MDL_EXP_NOLDS  // profiling builds only: no LDS request for k_step (valid only while no env resets)
+    if (envs_per_wave == 1) lds = 0;
+#endif
+    const StepLaunch L = step_launch(p, actions, fmt, ids, n, auto_reset, r, sh, done, wpb, lds, K, envs_per_wave);
+    select_step<V>(p, envs_per_wave, [&](auto kernel, auto...) { L(kernel, s); });
+    return hipGetLastError();
+}
+
+hipError_t launch_step(const DevParams& p, const uint8_t* actions, int fmt, const int* ids, int n, int auto_reset,
+                       double* r, float* sh, uint8_t* done, int wpb, size_t lds, hipStream_t s, int envs_per_wave) {
+    // four and two envs per wave: full batch only, within the kernels' A and P
+    if (envs_per_wave != 1 && (ids || !(envs_per_wave == 4 ? step_rows_ok(p.A, p.P)
+                                                           : envs_per_wave == 2 && step_halves_ok(p.A, p.P))))
+        return hipErrorInvalidValue;
+    return launch_step_v<STEP_PLAIN>(p, actions, fmt, ids, n, auto_reset, r, sh, done, wpb, lds, 1, envs_per_wave, s);
+}
+
+hipError_t launch_step_fused(const DevParams& p, const uint8_t* actions, int fmt, const int* ids, int n, int K,
+                             int auto_reset, double* r, float* sh, uint8_t* done, int wpb, size_t lds,
+                             hipStream_t s) {
+    return launch_step_v<STEP_FUSED>(p, actions, fmt, ids, n, auto_reset, r, sh, done, wpb, lds, K, 1, s);
 }
 
 hipError_t launch_step_floor(const DevParams& p, int n, int wpb, size_t lds, hipStream_t s, int envs_per_wave) {
-    StepArgs a{};
-    a.p = p;
-    a.n = n;
-    a.wpb = wpb;
-    a.lds_stride = (int)lds;
-    a.K = 1;
-    const dim3 grid(blocks_for((n + envs_per_wave - 1) / envs_per_wave, wpb)), block(64 * wpb);
-    const uint32_t ap = pack_ap(p.A, p.P, (int)grid.x);
-    const uint32_t nw = (uint32_t)n | ((uint32_t)wpb << 24) | (p.env_map ? NW_MAP : 0u);
-    hipLaunchKernelGGL(k_step_floor, grid, block, lds * wpb, s, p.rob, p.pkg, p.pstate, (const u32x4*)p.es, p.trk,
-                       (const uint8_t*)nullptr, ap, nw, a);
+    step_launch(p, nullptr, 0, nullptr, n, 0, nullptr, nullptr, nullptr, wpb, lds, 1, envs_per_wave)(k_step_floor, s);
     return hipGetLastError();
-}
-
-template <bool ST, bool FUSED>
-static void launch_step_s(const DevParams& p, const uint8_t* actions, int fmt, const int* ids, int n, int auto_reset,
-                          double* r, float* sh, uint8_t* done, int wpb, size_t lds, int K, hipStream_t s) {
-    switch (nch_for(p.P)) {
-        case 1: launch_step_t<ST, 1, FUSED>(p, actions, fmt, ids, n, auto_reset, r, sh, done, wpb, lds, K, s); break;
-        case 2: launch_step_t<ST, 2, FUSED>(p, actions, fmt, ids, n, auto_reset, r, sh, done, wpb, lds, K, s); break;
-        case 4: launch_step_t<ST, 4, FUSED>(p, actions, fmt, ids, n, auto_reset, r, sh, done, wpb, lds, K, s); break;
-        case 8: launch_step_t<ST, 8, FUSED>(p, actions, fmt, ids, n, auto_reset, r, sh, done, wpb, lds, K, s); break;
-        default: launch_step_t<ST, 16, FUSED>(p, actions, fmt, ids, n, auto_reset, r, sh, done, wpb, lds, K, s); break;
-    }
-}
-
-template <bool ST, int NCH>
-static void launch_step_mail_t(const StepArgs& a, const uint8_t* actions, const MailArgs& ma, int inl, int wpb,
-                               size_t lds, hipStream_t s) {
-    const DevParams& p = a.p;
-    const dim3 grid(blocks_for(a.n, wpb)), block(64 * wpb);
-    const uint32_t ap = pack_ap(p.A, p.P, (int)grid.x);
-    const uint32_t nw = (uint32_t)a.n | ((uint32_t)wpb << 24) | (a.env_ids ? NW_IDS : 0u) | (p.env_map ? NW_MAP : 0u);
-#define MDL_STEP_ARGS p.rob, p.pkg, p.pstate, (const u32x4*)p.es, p.trk, actions, ap, nw, a, ma, inl
-    if (p.A <= 8) hipLaunchKernelGGL((k_step_mail<ST, NCH, 8>), grid, block, lds * wpb, s, MDL_STEP_ARGS);
-    else hipLaunchKernelGGL((k_step_mail<ST, NCH, 0>), grid, block, lds * wpb, s, MDL_STEP_ARGS);
-#undef MDL_STEP_ARGS
 }
 
 hipError_t launch_step_mail(const DevParams& p, const uint8_t* codes, const int* ids, int n, int auto_reset, double* r,
                             float* sh, uint8_t* done, int wpb, size_t lds, const MailRows& m, unsigned* ctr,
                             unsigned base, int32_t seq, hipStream_t s) {
-    StepArgs a;
-    a.p = p;
-    a.actions = codes;
-    a.env_ids = ids;
-    a.r_out = r;
-    a.sh_out = sh;
-    a.done_out = done;
-    a.fmt = 1;   // MDL_ACTION_CODES (decode_action)
-    a.n = n;
-    a.auto_reset = auto_reset;
-    a.wpb = wpb;
-    a.lds_stride = (int)lds;
-    a.K = 1;
+    // fmt 1: MDL_ACTION_CODES (decode_action)
+    const StepLaunch L = step_launch(p, codes, 1, ids, n, auto_reset, r, sh, done, wpb, lds, 1, 1);
     MailArgs ma;
     ma.m = m;
     ma.pb = Publish{m.seq, ctr, base, seq, (unsigned)n};
     const size_t nb = (size_t)n * p.A;
     const int inl = nb <= (size_t)MAIL_INLINE_CODES;
     if (inl) std::memcpy(ma.codes, codes, nb);
-    const bool st = p.stale != 0;
-    switch (nch_for(p.P)) {
-        case 1: st ? launch_step_mail_t<true, 1>(a, codes, ma, inl, wpb, lds, s) : launch_step_mail_t<false, 1>(a, codes, ma, inl, wpb, lds, s); break;
-        case 2: st ? launch_step_mail_t<true, 2>(a, codes, ma, inl, wpb, lds, s) : launch_step_mail_t<false, 2>(a, codes, ma, inl, wpb, lds, s); break;
-        case 4: st ? launch_step_mail_t<true, 4>(a, codes, ma, inl, wpb, lds, s) : launch_step_mail_t<false, 4>(a, codes, ma, inl, wpb, lds, s); break;
-        case 8: st ? launch_step_mail_t<true, 8>(a, codes, ma, inl, wpb, lds, s) : launch_step_mail_t<false, 8>(a, codes, ma, inl, wpb, lds, s); break;
-        default: st ? launch_step_mail_t<true, 16>(a, codes, ma, inl, wpb, lds, s) : launch_step_mail_t<false, 16>(a, codes, ma, inl, wpb, lds, s); break;
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_step(const DevParams& p, const uint8_t* actions, int fmt, const int* ids, int n, int auto_reset,
-                       double* r, float* sh, uint8_t* done, int wpb, size_t lds, hipStream_t s) {
-    if (p.stale) launch_step_s<true, false>(p, actions, fmt, ids, n, auto_reset, r, sh, done, wpb, lds, 1, s);
-    else launch_step_s<false, false>(p, actions, fmt, ids, n, auto_reset, r, sh, done, wpb, lds, 1, s);
+    select_step<STEP_MAIL>(p, 1, [&](auto kernel, auto...) { L(kernel, s, ma, inl); });
     return hipGetLastError();
 }
 
@@ -1982,32 +1933,9 @@ hipError_t launch_step_obs(const DevParams& p, const uint8_t* actions, int fmt, 
                            float* sh, uint8_t* done, float* amap, float* avec, float* cmap, float* cvec, int wpb,
                            size_t lds, hipStream_t s) {
     if (nch_for(p.P) != 1 || p.A > 8 || !p.obs_small) return hipErrorInvalidValue;
-    StepArgs a;
-    a.p = p;
-    a.actions = actions;
-    a.env_ids = nullptr;
-    a.r_out = r;
-    a.sh_out = sh;
-    a.done_out = done;
-    a.fmt = fmt;
-    a.n = n;
-    a.auto_reset = auto_reset;
-    a.wpb = wpb;
-    a.lds_stride = (int)lds;
-    a.K = 1;
+    const StepLaunch L = step_launch(p, actions, fmt, nullptr, n, auto_reset, r, sh, done, wpb, lds, 1, 1);
     const ObsArgs o{amap, avec, cmap, cvec};
-    const dim3 grid(blocks_for(n, wpb)), block(64 * wpb);
-    const uint32_t ap = pack_ap(p.A, p.P, (int)grid.x);
-    const uint32_t nw = (uint32_t)n | ((uint32_t)wpb << 24) | (p.env_map ? NW_MAP : 0u);
-#define MDL_STEP_ARGS p.rob, p.pkg, p.pstate, (const u32x4*)p.es, p.trk, actions, ap, nw, a, o
-    if (p.stale) {
-        if (p.A == 5) hipLaunchKernelGGL((k_step_obs<true, 5>), grid, block, lds * wpb, s, MDL_STEP_ARGS);
-        else hipLaunchKernelGGL((k_step_obs<true, 8>), grid, block, lds * wpb, s, MDL_STEP_ARGS);
-    } else {
-        if (p.A == 5) hipLaunchKernelGGL((k_step_obs<false, 5>), grid, block, lds * wpb, s, MDL_STEP_ARGS);
-        else hipLaunchKernelGGL((k_step_obs<false, 8>), grid, block, lds * wpb, s, MDL_STEP_ARGS);
-    }
-#undef MDL_STEP_ARGS
+    select_step<STEP_OBS>(p, 1, [&](auto kernel, auto...) { L(kernel, s, o); });
     return hipGetLastError();
 }
 
@@ -2039,14 +1967,6 @@ hipError_t launch_views_idq_reward(const int32_t* prev, const int64_t* prev_offs
                                    hipStream_t s) {
     hipLaunchKernelGGL(k_views_idq_reward, dim3(blocks_for(n, wpb)), dim3(256), lds * wpb, s, prev, prev_offs, cur,
                        cur_offs, ops, op_offs, ops_are_ints, n, out, wpb, (int)lds, NSmax);
-    return hipGetLastError();
-}
-
-hipError_t launch_step_fused(const DevParams& p, const uint8_t* actions, int fmt, const int* ids, int n, int K,
-                             int auto_reset, double* r, float* sh, uint8_t* done, int wpb, size_t lds,
-                             hipStream_t s) {
-    if (p.stale) launch_step_s<true, true>(p, actions, fmt, ids, n, auto_reset, r, sh, done, wpb, lds, K, s);
-    else launch_step_s<false, true>(p, actions, fmt, ids, n, auto_reset, r, sh, done, wpb, lds, K, s);
     return hipGetLastError();
 }
 

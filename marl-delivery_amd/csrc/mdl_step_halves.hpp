@@ -1,6 +1,6 @@
 // mdl_step_halves.hpp -- the step kernel with TWO ENVS PER WAVEFRONT, one per 32-lane half, for
-// the eight-to-sixteen-robot configurations (8 <= A <= 16, P <= 128: BASELINE config 5's 16 robots
-// and 100 packages).  Included by mdl_kernels.hip after mdl_step_rows.hpp; same reference semantics
+// the sixteen-robot configurations (A == 16, P <= 128: BASELINE config 5's 16 robots and 100
+// packages).  Included by mdl_kernels.hip after mdl_step_rows.hpp; same reference semantics
 // (env.py:173-316, MAPPO/helper.py:257-369, MAPPO/trainer.py:95-130,211-259).
 //
 // Why: k_step<.., 16> runs one env per wave and is issue bound at config 5's 131,072 envs (~395
@@ -25,6 +25,7 @@
 
 constexpr int HALF = 32;                 // lanes per env
 constexpr int HALF_NC = 4;               // package chunks per lane: P <= 128
+constexpr int HALVES_MAX_P = HALF * HALF_NC;   // step_halves_ok's limit
 constexpr int HALF_CAND = 136;           // candidate slots per half (<= 128 candidates, padded to a multiple of 4)
 
 // minimum over the 32 lanes of this lane's half, on every lane of the half
@@ -53,6 +54,10 @@ __global__ __launch_bounds__(256) void k_step_halves(const uint32_t* __restrict_
                                                      StepArgs args) {
     constexpr int NC = HALF_NC;
     constexpr uint32_t NONE = 255u;   // no package slot (slots < 128)
+    // the unclamped package loads below: element lb + c * HALF past the wave's first env, lb = hh * P + hl
+    // masked to 8 bits -- the second half (hh = 1) of the largest P, its last lane and chunk
+    constexpr int MAX_OFF = (2 - 1) * HALVES_MAX_P + (HALF - 1) + (HALF_NC - 1) * HALF;
+    static_assert(MAX_OFF < PKG_PAD && MAX_OFF <= 0xff, "k_step_halves: package loads stay inside the buffers' padding");
     extern __shared__ __align__(16) unsigned char smem[];
     const DevParams& p = args.p;
     const int A = (int)(ap & 0x7fu), P = (int)((ap >> 7) & 0x7ffu);
@@ -446,8 +451,8 @@ __global__ __launch_bounds__(256) void k_step_halves(const uint32_t* __restrict_
         s = s + t5v;
         s_lane = fmask(Mact, s);
     }
-    // numpy's pairwise float32 sum of the A (8..16) agents, in-row: lanes A..15 hold +0.0f, so every
-    // A in 8..16 takes numpy's n >= 8 form r_j = x_j + x_{j+8}, ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7))
+    // numpy's pairwise float32 sum of the A == 16 agents (step_halves_ok), in-row: numpy's n >= 8 form
+    // r_j = x_j + x_{j+8}, ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7))
     float ssum;
     {
         const float r8 = s_lane + dppf<0x128>(s_lane);   // row_ror:8: lane j < 8 gets x_j + x_{j+8}

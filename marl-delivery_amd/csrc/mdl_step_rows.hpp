@@ -21,6 +21,7 @@
 
 constexpr int ROW = 16;        // lanes per env
 // package chunks per lane: NC = 4 (P <= 64), the only form built (a template parameter of the kernel)
+constexpr int ROWS_MAX_P = ROW * 4;   // step_rows_ok's limit
 
 // lane J of this lane's row, on every lane of the row (DPP row_newbcast, gfx90a+)
 template <int J>
@@ -85,6 +86,7 @@ __host__ __device__ constexpr size_t rows_scratch_bytes(int NC) { return (size_t
 // where a resetting wave keeps its state words during the reset: the slice's last 512 bytes, past the
 // reset scratch of P <= 64 packages (reset_lds_bytes(64) = 3,712 <= 3,840)
 constexpr size_t ROWS_PS_STASH = rows_scratch_bytes(4) - 4 * 64 * 2;
+static_assert(reset_lds_bytes(ROWS_MAX_P) <= ROWS_PS_STASH, "k_step_rows: the reset scratch ends before the stashed state words");
 // one flag byte per package slot, a lane's NC slots in one load
 template <int NC> struct FlagWord;
 template <> struct FlagWord<4> { typedef uint32_t T; };
@@ -103,6 +105,10 @@ __global__ __launch_bounds__(256) void k_step_rows(const uint32_t* __restrict__ 
                                                    StepArgs args) {
     static_assert(AU >= 1 && AU <= 8, "k_step_rows: A <= 8");
     static_assert(NC == 4, "k_step_rows: P <= 64 (the only form built and tested)");
+    // the unclamped package loads below: element lb + c * ROW past the wave's first env, lb = re * P + rl
+    // masked to 8 bits -- the last row (re = 3) of the largest P, its last lane and chunk
+    constexpr int MAX_OFF = (4 - 1) * ROWS_MAX_P + (ROW - 1) + (NC - 1) * ROW;
+    static_assert(MAX_OFF < PKG_PAD && MAX_OFF <= 0xff, "k_step_rows: package loads stay inside the buffers' padding");
     constexpr uint32_t NONE = 255u;   // no package slot (slots < 16 * NC <= 128)
     extern __shared__ __align__(16) unsigned char smem[];
     const DevParams& p = args.p;

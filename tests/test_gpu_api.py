@@ -155,3 +155,36 @@ def test_vectorized_env_repeated_and_negative_indices():
     assert len(s) == 1
     st = v1.reset(indices=[1, 1])
     assert len(st) == 2
+
+
+# (map, A, P, tracker, layout, with_obs, symbol): the step dispatch written out by hand -- STALE from
+# the tracker, NCH = chunks of 64 packages rounded up to 1, 2, 4, 8, 16, then AU = A for A = 5 / 16
+# up to two chunks, else 8 for A <= 8, else 0; rows: AU 5 or 8, NFULL 3 from P = 48; halves: NFULL 3
+# from P = 96; the fused step + observation kernel: AU 5 or 8
+KERNEL_NAMES = [
+    ("map1.txt", 5, 50, "mappo", "wave", False, "mdl::k_step<true, 1, false, 5>"),
+    ("map2.txt", 16, 100, "mappo", "wave", False, "mdl::k_step<true, 2, false, 16>"),
+    ("map1.txt", 3, 10, "fresh", "wave", False, "mdl::k_step<false, 1, false, 8>"),
+    ("map2.txt", 5, 200, "mappo", "wave", False, "mdl::k_step<true, 4, false, 8>"),
+    ("map2.txt", 20, 300, "fresh", "wave", False, "mdl::k_step<false, 8, false, 0>"),
+    ("map1.txt", 9, 600, "mappo", "wave", False, "mdl::k_step<true, 16, false, 0>"),
+    ("map1.txt", 8, 128, "fresh", "wave", False, "mdl::k_step<false, 2, false, 8>"),
+    ("map2.txt", 16, 129, "mappo", "wave", False, "mdl::k_step<true, 4, false, 0>"),
+    ("map2.txt", 8, 40, "fresh", "rows", False, "mdl::k_step_rows<false, 8, 4, 0>"),
+    ("map1.txt", 5, 48, "mappo", "rows", False, "mdl::k_step_rows<true, 5, 4, 3>"),
+    ("map1.txt", 5, 47, "mappo", "rows", False, "mdl::k_step_rows<true, 5, 4, 0>"),
+    ("map2.txt", 16, 95, "fresh", "halves", False, "mdl::k_step_halves<false, 0>"),
+    ("map2.txt", 16, 96, "mappo", "halves", False, "mdl::k_step_halves<true, 3>"),
+    ("map1.txt", 4, 20, "fresh", "wave", True, "mdl::k_step_obs<false, 8>"),
+    ("map1.txt", 5, 64, "mappo", "wave", True, "mdl::k_step_obs<true, 5>"),
+]
+
+
+@pytest.mark.parametrize("mapname,A,P,tracker,layout,with_obs,want", KERNEL_NAMES,
+                         ids=[f"A{c[1]}-P{c[2]}-{c[3]}-{'obs' if c[5] else c[4]}" for c in KERNEL_NAMES])
+def test_step_kernel_name_table(mapname, A, P, tracker, layout, with_obs, want):
+    """The symbol the engine reports for a step launch (what bench.py labels its roofline record
+    with) against the dispatch rule written out as literals; no stepping."""
+    env = _mg().BatchedEnv(grid(mapname), 8, A, P, 20, seed=1, tracker=tracker, max_packages_obs=5)
+    assert env.step_kernel_name(layout, with_obs=with_obs) == want
+    env.close()

@@ -161,3 +161,28 @@ def test_halves_auto_threshold():
         assert torch.equal(r1, r2) and torch.equal(s1.view(torch.int32), s2.view(torch.int32)) and torch.equal(d1, d2)
     torch.cuda.synchronize()
     assert np.array_equal(big.save_state(), ref.save_state())
+
+
+def _grid_20x70():
+    """A generated 20 x 70 map: wider than 64 columns, so the engine leaves NW_SMALLMAP clear and
+    k_step_halves takes its per-robot pick-up scan instead of the 64 x 64 cell bitmap."""
+    from test_gpu_random_maps import _random_grid
+    return _random_grid(np.random.RandomState(70), 20, 70, 0.15)
+
+
+@pytest.mark.parametrize("tracker", ["mappo", "fresh"])
+def test_halves_equals_wave_map_wider_than_64(tracker):
+    """Every packaged map fits 64 x 64; this one does not.  E = 7: the last wave's second half is empty."""
+    T = 20
+    a, b = _pair(_grid_20x70(), 7, 16, 40, T, seed=31, tracker=tracker)
+    assert _run(a, b, 2 * T + 5, seed=12) > 0
+    assert b.last_step_layout() == "halves"
+
+
+def test_halves_equals_wave_mixed_maps_one_wider_than_64():
+    """One map over 64 columns clears the flag for the whole engine: the envs on map2 take the scan too."""
+    T = 20
+    env_map = np.arange(9) % 2
+    a, b = _pair([grid("map2.txt"), _grid_20x70()], 9, 16, 40, T, seed=33, tracker="mappo", env_map=env_map)
+    assert _run(a, b, 2 * T + 5, seed=14) > 0
+    assert b.last_step_layout() == "halves"
