@@ -129,6 +129,25 @@ int mdl_step_obs(MdlEngine* eng, const uint8_t* actions, int32_t action_format, 
                  float* r_shaped, uint8_t* done, float* actor_map, float* actor_vec, float* critic_map,
                  float* critic_vec, void* stream);
 
+/* One transition of a QMIX episode batch (QMIX/trainer.py:333-526 steps only the envs whose episode
+ * is still running): the full batch, row w = env w, the envs sharing one map shape as in mdl_step_obs.
+ * active: DEVICE uint8 [E], the caller's, read and updated on the device (no host round trip).
+ *   active[e] != 0: exactly mdl_step with auto_reset = 0 on env e (state, fp64 reward, shaped
+ *     reward, done, tracker update, episode results: bit for bit), then mdl_build_obs of its new
+ *     state into row e of the four observation tensors; filled[e] = 1; active[e] is cleared when
+ *     the env is done after the step.
+ *   active[e] == 0: nothing of env e is touched; r_env[e] = r_shaped[e] = done[e] = filled[e] = 0
+ *     and its rows of the observation tensors are NOT written.
+ * The launch steps whatever `active` marks -- it does not check whether an env is past its last
+ * step -- and never resets.  r_env / r_shaped / done / filled ([E], device) and the observation
+ * pointers may be NULL.  Where mdl_step_obs is one kernel (the small builder, A <= 8, P <= 64)
+ * this is one kernel too (an inactive env's wave reads its mask byte and leaves); otherwise a
+ * fixed sequence of launches (mask -> id list, the subset step, mask update, the builder over the
+ * stepped rows), also without host synchronisation, so either form can be captured in a hipGraph. */
+int mdl_step_episode(MdlEngine* eng, const uint8_t* actions, int32_t action_format, uint8_t* active, double* r_env,
+                     float* r_shaped, uint8_t* done, uint8_t* filled, float* actor_map, float* actor_vec,
+                     float* critic_map, float* critic_vec, void* stream);
+
 /* Bench mode: k_steps consecutive mdl_step calls fused
  * into one launch, each env's state held in registers between steps.  Same
  * results as k_steps mdl_step calls with actions[k] (bit-exact); actions are
@@ -272,6 +291,30 @@ int mdl_sample_actions(const float* logits, int64_t n_rows, int32_t n_actions, u
 int mdl_sample_actions_dev(const float* logits, int64_t n_rows, int32_t n_actions, uint64_t seed,
                            const uint64_t* offset_dev, uint64_t offset_add, uint8_t* actions, float* log_probs,
                            void* stream);
+
+/* Epsilon-greedy action selection over Q-values (QMIX/trainer.py:298-319), the library's random
+ * stream in place of torch's.  q: float32 [n_rows][n_actions]; avail: uint8 of the same shape
+ * (non-zero = available) or NULL = every action available; actions: uint8 [n_rows].  Per row:
+ *   (x0, x1, x2, x3) = Philox4x32-10(counter = (offset lo, offset hi, row lo, row hi),
+ *                                    key = (seed lo, seed hi))      -- mdl_sample_actions's keying
+ *   explore  iff  float(x0 >> 8) * 2^-24 < epsilon   (a float32 compare: epsilon = 0 never
+ *                                                     explores, epsilon = 1 always does)
+ *   exploring row: the k-th available action in index order (k from 0),
+ *                  k = (uint64(x1) * n_avail) >> 32
+ *   any other row: best = the first available action; then every later available action i, in
+ *                  index order, replaces it iff q[i] > q[best], or q[best] is a NaN and q[i] is
+ *                  not -- the lowest index among the available actions with the largest q; a NaN
+ *                  never wins over a number
+ *   a row with no available action gets 0.
+ * Deterministic for a given (seed, offset) and independent of the launch shape; a caller advances
+ * `offset` once per call.  The _dev form reads epsilon = *epsilon_dev and offset = *offset_dev +
+ * offset_add on the device, so a captured episode replays with fresh values; identical results to
+ * the host form at the same values. */
+int mdl_select_actions_eps(const float* q, const uint8_t* avail, int64_t n_rows, int32_t n_actions, float epsilon,
+                           uint64_t seed, uint64_t offset, uint8_t* actions, void* stream);
+int mdl_select_actions_eps_dev(const float* q, const uint8_t* avail, int64_t n_rows, int32_t n_actions,
+                               const float* epsilon_dev, uint64_t seed, const uint64_t* offset_dev,
+                               uint64_t offset_add, uint8_t* actions, void* stream);
 
 /* *counter += value on the device (stream-ordered; advances offset_dev inside a graph). */
 int mdl_counter_add(uint64_t* counter, uint64_t value, void* stream);

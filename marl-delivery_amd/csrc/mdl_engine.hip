@@ -209,11 +209,24 @@ struct MdlEngine {
     // Every observation build goes through here: the env range must lie inside one run of
     // same-shape envs (the small builder copies the rank table of the range's first env's map
     // into LDS for the whole launch, mdl_obs_small.hpp k_obs_small; the outputs have one H x W).
-    hipError_t launch_obs(int env_begin, int n, float* am, float* av, float* cm, float* cv, hipStream_t s) const {
+    hipError_t launch_obs(int env_begin, int n, float* am, float* av, float* cm, float* cv, hipStream_t s,
+                          const uint8_t* mask = nullptr) const {
         if (env_begin < 0 || n <= 0 || env_begin + n > p.E || shape_run_end[env_begin] < env_begin + n)
             return hipErrorInvalidValue;
-        return mdl::launch_obs(p, env_begin, n, am, av, cm, cv, wpb_obs, lds_obs, s, obs_rank_lds);
+        return mdl::launch_obs(p, env_begin, n, am, av, cm, cv, wpb_obs, lds_obs, s, obs_rank_lds, mask);
     }
+    // The per-wave LDS slice of the one-launch step + observation kernels (mdl_step_obs,
+    // mdl_step_episode): the reset scratch, then the planes.  0 where they do not apply (the general
+    // builder, A > 8, P > 64, or a slice over the budget): the call is then a sequence of launches.
+    size_t fused_obs_lds() const {
+        if (!(p.obs_small && p.A <= 8 && p.P <= 64)) return 0;
+        const size_t lds = std::max(lds_step, lds_obs);
+        return lds <= LDS_BUDGET ? lds : 0;
+    }
+    // mdl_step_episode's scratch outside the one-launch form: the step's id list, and the filled /
+    // done bytes a caller did not ask for
+    int* epi_ids = nullptr;
+    uint8_t *epi_filled = nullptr, *epi_done = nullptr;
 
     template <class T>
     int alloc(T** ptr, size_t count) {
@@ -421,6 +434,9 @@ int mdl_create(const MdlConfig* cfg, const uint8_t* grids, const int32_t* map_hw
     rc |= eng->alloc(&p.trk, (p.stale ? E : 1) * P + mdl::PKG_PAD);
     rc |= eng->alloc(&p.ep_total, E);
     rc |= eng->alloc(&p.ep_len, E);
+    rc |= eng->alloc(&eng->epi_ids, E);
+    rc |= eng->alloc(&eng->epi_filled, E);
+    rc |= eng->alloc(&eng->epi_done, E);
     if (rc) {
         std::string msg = g_err;
         delete eng;
@@ -609,19 +625,48 @@ int mdl_step_obs(MdlEngine* eng, const uint8_t* actions, int32_t action_format, 
                     "per group", eng->shape_run_end[0]);
     DeviceGuard dg(eng->device);
     hipStream_t s = (hipStream_t)stream;
-    if (eng->p.obs_small && eng->p.A <= 8 && eng->p.P <= 64) {
-        const size_t lds = std::max(eng->lds_step, eng->lds_obs);   // one slice: reset scratch, then the planes
-        if (lds <= LDS_BUDGET) {   // else: the two-launch path below
-            const int wpb = step_wpb(E, eng->n_cu, lds, eng->p.P);
-            HIPCHK(mdl::launch_step_obs(eng->p, actions, action_format, E, auto_reset, r_env, r_shaped, done,
-                                        actor_map, actor_vec, critic_map, critic_vec, wpb, lds, s));
-            return 0;
-        }
+    if (const size_t lds = eng->fused_obs_lds()) {   // else: the two-launch path below
+        const int wpb = step_wpb(E, eng->n_cu, lds, eng->p.P);
+        HIPCHK(mdl::launch_step_obs(eng->p, actions, action_format, E, auto_reset, r_env, r_shaped, done,
+                                    actor_map, actor_vec, critic_map, critic_vec, wpb, lds, s));
+        return 0;
     }
     const auto sh = eng->step_shape(MDL_STEP_LAYOUT_WAVE, E);
     HIPCHK(mdl::launch_step(eng->p, actions, action_format, nullptr, E, auto_reset, r_env, r_shaped, done, sh.wpb,
                             sh.lds, s));
     HIPCHK(eng->launch_obs(0, E, actor_map, actor_vec, critic_map, critic_vec, s));
+    return 0;
+}
+
+int mdl_step_episode(MdlEngine* eng, const uint8_t* actions, int32_t action_format, uint8_t* active, double* r_env,
+                     float* r_shaped, uint8_t* done, uint8_t* filled, float* actor_map, float* actor_vec,
+                     float* critic_map, float* critic_vec, void* stream) {
+    if (!eng || !actions || !active) return fail("mdl_step_episode: null argument");
+    if (!eng->seeded) return fail("mdl_step_episode: engine not seeded (call mdl_seed first)");
+    if (action_format != MDL_ACTION_TRAINER_INT && action_format != MDL_ACTION_CODES)
+        return fail("mdl_step_episode: unknown action_format %d", action_format);
+    const int E = eng->p.E;
+    if (eng->shape_run_end[0] < E)
+        return fail("mdl_step_episode: the envs mix map shapes (same-shape run ends at %d)", eng->shape_run_end[0]);
+    DeviceGuard dg(eng->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (const size_t lds = eng->fused_obs_lds()) {
+        const int wpb = step_wpb(E, eng->n_cu, lds, eng->p.P);
+        HIPCHK(mdl::launch_step_episode(eng->p, actions, action_format, E, active, r_env, r_shaped, done, filled,
+                                        actor_map, actor_vec, critic_map, critic_vec, wpb, lds, s));
+        return 0;
+    }
+    // The other shapes: mask -> id list (-1 = skipped by k_step) and zero rows, the subset step without
+    // reset, the mask update, then the builder over the rows that were stepped.  No host round trip.
+    uint8_t* fl = filled ? filled : eng->epi_filled;
+    uint8_t* dn = done ? done : eng->epi_done;
+    HIPCHK(mdl::launch_episode_begin(active, E, eng->epi_ids, fl, r_env, r_shaped, dn, s));
+    const auto sh = eng->step_shape(MDL_STEP_LAYOUT_WAVE, E);
+    HIPCHK(mdl::launch_step(eng->p, actions, action_format, eng->epi_ids, E, 0, r_env, r_shaped, dn, sh.wpb, sh.lds,
+                            s));
+    HIPCHK(mdl::launch_episode_end(active, fl, dn, E, s));
+    if (actor_map || actor_vec || critic_map || critic_vec)
+        HIPCHK(eng->launch_obs(0, E, actor_map, actor_vec, critic_map, critic_vec, s, fl));
     return 0;
 }
 
@@ -1246,8 +1291,7 @@ int mdl_step_kernel_name(const MdlEngine* eng, int32_t layout, int32_t with_obs,
         (layout == MDL_STEP_LAYOUT_HALVES && (with_obs || !eng->step_halves)))
         return fail("mdl_step_kernel_name: no launch in layout %d in this configuration", layout);
     // mdl_step_obs's one-launch form (else it is mdl_step's wave kernel + the builder)
-    const bool obs = with_obs && eng->p.obs_small && eng->p.A <= 8 && eng->p.P <= 64 &&
-                     std::max(eng->lds_step, eng->lds_obs) <= LDS_BUDGET;
+    const bool obs = with_obs && eng->fused_obs_lds() != 0;
     const int k = mdl::step_kernel_name(eng->p, eng->step_shape(layout, eng->p.E).epw, obs, out, cap);
     if (k < 0 || k >= cap) return fail("mdl_step_kernel_name: buffer of %d bytes too small", cap);
     return 0;

@@ -360,6 +360,17 @@ struct ObsArgs {
     float* cvec;
 };
 
+// The episode form's extra arguments (mdl_step_episode, after ObsArgs): the caller's per-env mask,
+// read and cleared on the device, and the per-row "this env was stepped" byte (may be null).
+struct EpiArgs {
+    uint8_t* active;
+    uint8_t* filled;
+};
+// EpiArgs follows StepArgs and ObsArgs in k_step_episode's kernarg segment
+typedef __attribute__((address_space(4))) const EpiArgs* EpiKargPtr;
+constexpr size_t EPI_KARG_OFF = sizeof(StepArgs) + sizeof(ObsArgs);
+static_assert(sizeof(StepArgs) % 8 == 0 && sizeof(ObsArgs) % 8 == 0, "EpiArgs starts where ObsArgs ends");
+
 // the completion tail of a Publish launch (every wave of the grid runs it, or the `expect`
 // waves that reach it); a one-wave launch (ctr == nullptr) publishes straight after its release
 __device__ __forceinline__ void publish_tail(const Publish& pb) {
@@ -394,6 +405,11 @@ struct MailArgs {
 // after every env.step -- one launch and no state reload instead of k_step + k_obs_small.
 // MAIL: after the write-back the wave writes its env's mailbox rows and counts itself toward
 // the call's completion word (MailArgs).
+// EPI (with OBS, mdl_step_episode): one transition of the envs the caller's mask marks, never a
+// reset.  A wave whose mask byte is 0 writes its zero output row and leaves before the state
+// loads; an env that is done after the step gets its mask byte cleared.  The mask pointer is an
+// ordinary (late) kernel argument, so only this form reads it -- the other instantiations keep
+// their state loads first, straight from the preloaded SGPRs.
 // Sixteen-robot movement test: lane L compares robot L & 15 with robot 4 (L >> 4) + k;
 // the lanes where that partner has the lower index.
 __host__ __device__ constexpr uint64_t move_lt_lanes(int k) {
@@ -403,13 +419,14 @@ __host__ __device__ constexpr uint64_t move_lt_lanes(int k) {
     return m;
 }
 
-template <bool STALE, int NCH, bool FUSED, int AU, bool OBS, bool MAIL = false>
+template <bool STALE, int NCH, bool FUSED, int AU, bool OBS, bool MAIL = false, bool EPI = false>
 __device__ __forceinline__ void step_body(const uint32_t* __restrict__ rob_pre, const uint64_t* __restrict__ pkg_pre,
                                           const uint16_t* __restrict__ pst_pre, const u32x4* __restrict__ es_pre,
                                           const uint64_t* __restrict__ trk_pre, const uint8_t* __restrict__ act_pre,
                                           uint32_t ap, uint32_t nw, const StepArgs& args, const ObsArgs& oa,
                                           const MailArgs* ma = nullptr) {
     static_assert(!OBS || (NCH == 1 && !FUSED && AU > 0 && AU <= 8), "fused observations: P <= 64, A <= 8");
+    static_assert(!EPI || (OBS && !MAIL), "the episode form is the fused step + observation launch's");
     extern __shared__ __align__(16) unsigned char smem[];
     const DevParams& p = args.p;
     // (the other scalar arguments are read only after the state loads are issued: read
@@ -440,6 +457,27 @@ __device__ __forceinline__ void step_body(const uint32_t* __restrict__ rob_pre, 
     if (nw & NW_IDS) {   // subset stepping: one more load; an id outside [0, E) is skipped
         e = uni(((GLOBAL const int*)args.env_ids)[w]);
         if ((unsigned)e >= (unsigned)args.p.E) return;
+    }
+    if constexpr (EPI) {   // full batch (row w = env w): an env whose episode is over is not loaded
+        // The pointers come through an opaque copy of the segment pointer, as in the write-back: read
+        // from `args`, they would be kept in SGPRs across the whole step for the stores at its end.
+        KargPtr ka = (KargPtr)((__attribute__((address_space(4))) const char*)
+                                   __builtin_amdgcn_kernarg_segment_ptr() + offsetof(StepKarg, args));
+        asm volatile("" : "+s"(ka));
+        EpiKargPtr ke = (EpiKargPtr)((__attribute__((address_space(4))) const char*)ka + EPI_KARG_OFF);
+        if (!uni((int)((GLOBAL const uint8_t*)ke->active)[w])) {
+            if (lane == 0) {
+                GLOBAL double* r0 = (GLOBAL double*)ka->r_out;
+                GLOBAL float* sh0 = (GLOBAL float*)ka->sh_out;
+                GLOBAL uint8_t* dn0 = (GLOBAL uint8_t*)ka->done_out;
+                GLOBAL uint8_t* fl0 = (GLOBAL uint8_t*)ke->filled;
+                if (r0) r0[w] = 0.0;
+                if (sh0) sh0[w] = 0.0f;
+                if (dn0) dn0[w] = 0;
+                if (fl0) fl0[w] = 0;
+            }
+            return;
+        }
     }
 
     STAMP(2);
@@ -525,6 +563,8 @@ __device__ __forceinline__ void step_body(const uint32_t* __restrict__ rob_pre, 
     GLOBAL uint16_t* pstw;
     GLOBAL uint64_t* trkw;
     GLOBAL u32x4* esw;
+    GLOBAL uint8_t* epa = nullptr;   // EPI: the mask and the filled bytes
+    GLOBAL uint8_t* epf = nullptr;
     const int KK = FUSED ? K : 1;
     uint32_t rfl = 0;   // the last step's reward terms (EnvScalars::rterms)
     for (int k = 0; k < KK; k++) {
@@ -1003,7 +1043,7 @@ __device__ __forceinline__ void step_body(const uint32_t* __restrict__ rob_pre, 
         STAMP(9);
         // ---- tracker update with the new state; a done env that resets here skips
         // it and updates with the reset state instead (MAPPO/trainer.py:230-259) ----
-        const bool do_rst = done && auto_reset;
+        const bool do_rst = !EPI && done && auto_reset;
         // After an update, the present entries in transit are exactly the carried ones; with
         // no pick-up, no drop and no spawn at t1 the update is a no-op, so it is skipped.
         if (STALE && !do_rst && !(MDL_ABLATE & 2) && (tookany | dmask | spawned))
@@ -1072,6 +1112,11 @@ __device__ __forceinline__ void step_body(const uint32_t* __restrict__ rob_pre, 
             pstw = (GLOBAL uint16_t*)ka->p.pstate;
             trkw = (GLOBAL uint64_t*)ka->p.trk;
             esw = (GLOBAL u32x4*)ka->p.es;
+            if constexpr (EPI) {
+                EpiKargPtr ke = (EpiKargPtr)((__attribute__((address_space(4))) const char*)ka + EPI_KARG_OFF);
+                epa = (GLOBAL uint8_t*)ke->active;
+                epf = (GLOBAL uint8_t*)ke->filled;
+            }
         }
         pin(rop); pin(shp); pin(dnp); pin(robw); pin(pstw); pin(trkw); pin(esw);
         if (lane == 0) {
@@ -1083,6 +1128,10 @@ __device__ __forceinline__ void step_body(const uint32_t* __restrict__ rob_pre, 
             if (rop) rop[o] = rr;
             if (shp) shp[o] = shaped;
             if (dnp) dnp[o] = done ? 1 : 0;
+            if constexpr (EPI) {
+                if (epf) epf[w] = 1;
+                if (done) epa[w] = 0;
+            }
         }
     }  // steps
 
@@ -1189,6 +1238,47 @@ __global__ __launch_bounds__(256) MDL_STEP_ATTR(1, false) void k_step_obs(const 
     step_body<STALE, 1, false, AU, true>(rob_pre, pkg_pre, pst_pre, es_pre, trk_pre, act_pre, ap, nw, args, oa);
 }
 
+// mdl_step_episode: k_step_obs for the envs the caller's mask marks (EPI: never a reset)
+template <bool STALE, int AU>
+__global__ __launch_bounds__(256) MDL_STEP_ATTR(1, false) void k_step_episode(const uint32_t* __restrict__ rob_pre,
+                                                  const uint64_t* __restrict__ pkg_pre,
+                                                  const uint16_t* __restrict__ pst_pre,
+                                                  const u32x4* __restrict__ es_pre,
+                                                  const uint64_t* __restrict__ trk_pre,
+                                                  const uint8_t* __restrict__ act_pre, uint32_t ap, uint32_t nw,
+                                                  StepArgs args, ObsArgs oa, EpiArgs ea) {
+    step_body<STALE, 1, false, AU, true, false, true>(rob_pre, pkg_pre, pst_pre, es_pre, trk_pre, act_pre, ap, nw,
+                                                      args, oa);
+    (void)ea;   // read from the kernarg segment (EPI_KARG_OFF)
+}
+
+// mdl_step_episode outside the fused launch's shapes, around the subset k_step and the builder:
+// k_episode_begin turns the mask into the step's id list (-1 = skipped) and the builder's row
+// mask, and writes the zero rows of the envs left out; k_episode_end clears the mask of the
+// envs that are done.
+__global__ __launch_bounds__(256) void k_episode_begin(const uint8_t* __restrict__ active, int n,
+                                                       int* __restrict__ ids, uint8_t* __restrict__ filled,
+                                                       double* __restrict__ r, float* __restrict__ sh,
+                                                       uint8_t* __restrict__ done) {
+    const int e = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (e >= n) return;
+    const bool on = active[e] != 0;
+    ids[e] = on ? e : -1;
+    filled[e] = on ? 1 : 0;
+    if (!on) {
+        if (r) r[e] = 0.0;
+        if (sh) sh[e] = 0.0f;
+        done[e] = 0;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_episode_end(uint8_t* __restrict__ active, const uint8_t* __restrict__ filled,
+                                                     const uint8_t* __restrict__ done, int n) {
+    const int e = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (e >= n) return;
+    if (filled[e] && done[e]) active[e] = 0;
+}
+
 #include "mdl_step_rows.hpp"
 #include "mdl_step_halves.hpp"
 
@@ -1218,12 +1308,14 @@ __device__ inline ObsLdsPre obs_pre_carve(unsigned char* base, int P) {
 template <bool STALE>
 __global__ __launch_bounds__(256) void k_obs(DevParams p, int env_begin, int n, float* __restrict__ amap,
                                              float* __restrict__ avec, float* __restrict__ cmap,
-                                             float* __restrict__ cvec, int wpb, int lds_stride) {
+                                             float* __restrict__ cvec, int wpb, int lds_stride,
+                                             const uint8_t* __restrict__ mask) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int wave = wave_id();
     const int lane = lane_id();
     const int w = xcd_block() * wpb + wave;
     if (wave >= wpb || w >= n) return;
+    if (mask && !mask[w]) return;   // row mask (mdl_step_episode): the row stays unwritten
     const int e = env_begin + w;
     const int A = p.A, P = p.P;
     unsigned char* base = smem + (size_t)wave * lds_stride;
@@ -1782,7 +1874,7 @@ size_t step_halves_lds(int P) {
 
 // ---- the step launches: one kernel selection (select_step), one argument path (step_launch) ----
 // STEP_PLAIN: k_step, k_step_halves or k_step_rows by envs per wave (1, 2, 4); the others: one wave per env
-enum StepVariant { STEP_PLAIN, STEP_FUSED, STEP_OBS, STEP_MAIL };
+enum StepVariant { STEP_PLAIN, STEP_FUSED, STEP_OBS, STEP_MAIL, STEP_EPISODE };
 
 // f(std::integral_constant<int, V>{}) for the V of Vs... that equals v
 template <int... Vs, class F>
@@ -1804,6 +1896,11 @@ static void select_step(const DevParams& p, int envs_per_wave, F&& f) {
             with_int<5, 8>(A == 5 ? 5 : 8, [&](auto au) {
                 constexpr int AU = decltype(au)::value;
                 hit(k_step_obs<ST, AU>, "mdl::k_step_obs<%s, %d>", AU);
+            });
+        } else if constexpr (V == STEP_EPISODE) {   // k_step_obs's shapes
+            with_int<5, 8>(A == 5 ? 5 : 8, [&](auto au) {
+                constexpr int AU = decltype(au)::value;
+                hit(k_step_episode<ST, AU>, "mdl::k_step_episode<%s, %d>", AU);
             });
         } else if constexpr (V == STEP_MAIL) {
             with_int<1, 2, 4, 8, 16>(nch, [&](auto nc) {
@@ -1939,6 +2036,30 @@ hipError_t launch_step_obs(const DevParams& p, const uint8_t* actions, int fmt, 
     return hipGetLastError();
 }
 
+// k_step_episode (mdl_step_episode): k_step_obs's launch over the full batch, stepping the envs
+// whose `active` byte is set, never resetting
+hipError_t launch_step_episode(const DevParams& p, const uint8_t* actions, int fmt, int n, uint8_t* active, double* r,
+                               float* sh, uint8_t* done, uint8_t* filled, float* amap, float* avec, float* cmap,
+                               float* cvec, int wpb, size_t lds, hipStream_t s) {
+    if (nch_for(p.P) != 1 || p.A > 8 || !p.obs_small) return hipErrorInvalidValue;
+    const StepLaunch L = step_launch(p, actions, fmt, nullptr, n, 0, r, sh, done, wpb, lds, 1, 1);
+    const ObsArgs o{amap, avec, cmap, cvec};
+    const EpiArgs ea{active, filled};
+    select_step<STEP_EPISODE>(p, 1, [&](auto kernel, auto...) { L(kernel, s, o, ea); });
+    return hipGetLastError();
+}
+
+hipError_t launch_episode_begin(const uint8_t* active, int n, int* ids, uint8_t* filled, double* r, float* sh,
+                                uint8_t* done, hipStream_t s) {
+    hipLaunchKernelGGL(k_episode_begin, dim3((n + 255) / 256), dim3(256), 0, s, active, n, ids, filled, r, sh, done);
+    return hipGetLastError();
+}
+
+hipError_t launch_episode_end(uint8_t* active, const uint8_t* filled, const uint8_t* done, int n, hipStream_t s) {
+    hipLaunchKernelGGL(k_episode_end, dim3((n + 255) / 256), dim3(256), 0, s, active, filled, done, n);
+    return hipGetLastError();
+}
+
 size_t alt_obs_lds(int P, int HW) { return obs_pre_bytes(P) + alt_lds_bytes(HW); }
 size_t views_alt_lds(int NSmax, int HW) { return view_pre_bytes(NSmax) + alt_lds_bytes(HW); }
 
@@ -1971,12 +2092,13 @@ hipError_t launch_views_idq_reward(const int32_t* prev, const int64_t* prev_offs
 }
 
 hipError_t launch_obs(const DevParams& p, int env_begin, int n, float* amap, float* avec, float* cmap, float* cvec,
-                      int wpb, size_t lds, hipStream_t s, int rank_lds) {
+                      int wpb, size_t lds, hipStream_t s, int rank_lds, const uint8_t* mask) {
     if (p.obs_small) {
         const dim3 g(blocks_for(n, wpb)), b(256);
         const size_t dyn = (size_t)rank_lds + lds * wpb;
 #define MDL_OBS_SMALL(ST, RL) \
-    hipLaunchKernelGGL((k_obs_small<ST, RL>), g, b, dyn, s, p, env_begin, n, amap, avec, cmap, cvec, wpb, (int)lds, rank_lds)
+    hipLaunchKernelGGL((k_obs_small<ST, RL>), g, b, dyn, s, p, env_begin, n, amap, avec, cmap, cvec, wpb, (int)lds, rank_lds, \
+                       mask)
         if (p.stale) {
             if (rank_lds > 0) MDL_OBS_SMALL(true, true);
             else MDL_OBS_SMALL(true, false);
@@ -1989,10 +2111,10 @@ hipError_t launch_obs(const DevParams& p, int env_begin, int n, float* amap, flo
     }
     if (p.stale)
         hipLaunchKernelGGL(k_obs<true>, dim3(blocks_for(n, wpb)), dim3(256), lds * wpb, s, p, env_begin, n, amap,
-                           avec, cmap, cvec, wpb, (int)lds);
+                           avec, cmap, cvec, wpb, (int)lds, mask);
     else
         hipLaunchKernelGGL(k_obs<false>, dim3(blocks_for(n, wpb)), dim3(256), lds * wpb, s, p, env_begin, n, amap,
-                           avec, cmap, cvec, wpb, (int)lds);
+                           avec, cmap, cvec, wpb, (int)lds, mask);
     return hipGetLastError();
 }
 

@@ -39,12 +39,25 @@ hipError_t launch_step_fused(const DevParams& p, const uint8_t* actions, int fmt
 hipError_t launch_step_obs(const DevParams& p, const uint8_t* actions, int fmt, int n, int auto_reset, double* r,
                            float* sh, uint8_t* done, float* amap, float* avec, float* cmap, float* cvec, int wpb,
                            size_t lds, hipStream_t s);
+// mdl_step_episode's one launch (launch_step_obs's shapes): one transition of the envs whose
+// `active` byte is set and their observation rows, no reset; a done env's byte is cleared, the
+// other envs get zero outputs, filled = 0 and unwritten observation rows.
+hipError_t launch_step_episode(const DevParams& p, const uint8_t* actions, int fmt, int n, uint8_t* active, double* r,
+                               float* sh, uint8_t* done, uint8_t* filled, float* amap, float* avec, float* cmap,
+                               float* cvec, int wpb, size_t lds, hipStream_t s);
+// mdl_step_episode in the other shapes, around launch_step(ids) and launch_obs(mask = filled):
+// begin: ids[e] = e or -1 (skipped), filled[e] = active[e] != 0, zero r / sh / done rows of the
+// envs left out (r, sh may be null); end: active[e] = 0 where filled[e] and done[e].
+hipError_t launch_episode_begin(const uint8_t* active, int n, int* ids, uint8_t* filled, double* r, float* sh,
+                                uint8_t* done, hipStream_t s);
+hipError_t launch_episode_end(uint8_t* active, const uint8_t* filled, const uint8_t* done, int n, hipStream_t s);
 // rank_lds > 0 (small builder): bytes of LDS in front of the per-wave slices holding the launch's
 // distance-rank table (mdl_obs_small.hpp k_obs_small).  PRECONDITION: envs [env_begin, env_begin+n)
 // share one map shape -- the table copied is env_begin's map's.  The engine checks it
-// (MdlEngine::launch_obs, mdl_engine.hip) before every call.
+// (MdlEngine::launch_obs, mdl_engine.hip) before every call.  mask (device, [n], may be null):
+// row w is built only where mask[w] != 0, the other rows stay unwritten.
 hipError_t launch_obs(const DevParams& p, int env_begin, int n, float* amap, float* avec, float* cmap, float* cvec,
-                      int wpb, size_t lds, hipStream_t s, int rank_lds = 0);
+                      int wpb, size_t lds, hipStream_t s, int rank_lds = 0, const uint8_t* mask = nullptr);
 // A launch's own completion word (host-mapped): every wave of its grid counts itself in the
 // running device counter `ctr` (never reset: `base` is its value before the launch) after a
 // system-scope release of its stores; the last one writes `value` to `seq`.  seq == nullptr: none;

@@ -674,7 +674,8 @@ __device__ __forceinline__ void obs_small_emit(const DevParams& p, int w, int mi
 template <bool STALE, bool RL>
 __global__ __launch_bounds__(256) void k_obs_small(DevParams p, int env_begin, int n, float* __restrict__ amap,
                                                    float* __restrict__ avec, float* __restrict__ cmap,
-                                                   float* __restrict__ cvec, int wpb, int lds_stride, int rank_lds) {
+                                                   float* __restrict__ cvec, int wpb, int lds_stride, int rank_lds,
+                                                   const uint8_t* __restrict__ mask) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int wave = wave_id();
     const int lane = lane_id();
@@ -688,6 +689,7 @@ __global__ __launch_bounds__(256) void k_obs_small(DevParams p, int env_begin, i
     }
     const int w = xcd_block() * wpb + wave;
     if (wave >= wpb || w >= n) return;
+    if (mask && !mask[w]) return;   // row mask (mdl_step_episode): the row stays unwritten
     const int e = env_begin + w;
     const int A = p.A, P = p.P;
     const int mi = p.env_map ? p.env_map[e] : 0;

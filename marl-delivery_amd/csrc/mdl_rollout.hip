@@ -5,6 +5,8 @@
 //   k_sample  Categorical(logits).sample() + log_prob   MAPPO/trainer.py:141-143
 //             (inverse CDF of softmax(logits) on a Philox4x32-10 uniform;
 //             the stream is this library's own, keyed by (seed, offset, row))
+//   k_select_eps  epsilon-greedy selection over Q-values   QMIX/trainer.py:298-319
+//             (the same Philox keying; include/mdl_engine.h states the draw)
 //   k_gae     the GAE recursion of MAPPO/trainer.py:266-276, same float32
 //             operation order as the reference's torch expressions
 #include <hip/hip_runtime.h>
@@ -112,6 +114,58 @@ __global__ __launch_bounds__(256) void k_gae(const float* __restrict__ r, const 
     }
 }
 
+// Epsilon-greedy selection over Q-values (QMIX/trainer.py:298-319), one row per thread.  The row's
+// Philox block is k_sample's: counter (offset, row), key (seed); x0 decides exploration in float32
+// (u < epsilon, u a 24-bit uniform in [0, 1)), x1 picks the k-th available action of an exploring
+// row, k = (x1 * n_avail) >> 32.  Any other row takes the first index among the available actions
+// with the largest q (compare `>`: a NaN never wins while the row has an available number).  A row
+// with no available action gets 0.
+// eps_dev / off_dev (graph-capturable form): epsilon = *eps_dev, offset = *off_dev + off_lo|off_hi<<32.
+__global__ __launch_bounds__(256) void k_select_eps(const float* __restrict__ q, const uint8_t* __restrict__ avail,
+                                                    int64_t n_rows, int n_act, float epsilon, uint32_t k0,
+                                                    uint32_t k1, uint32_t off_lo, uint32_t off_hi,
+                                                    const float* __restrict__ eps_dev,
+                                                    const uint64_t* __restrict__ off_dev,
+                                                    uint8_t* __restrict__ actions) {
+    const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= n_rows) return;
+    if (off_dev) {
+        const uint64_t o = *off_dev + ((uint64_t)off_hi << 32 | off_lo);
+        off_lo = (uint32_t)o;
+        off_hi = (uint32_t)(o >> 32);
+    }
+    if (eps_dev) epsilon = *eps_dev;
+    const float* qr = q + row * n_act;
+    const uint8_t* av = avail ? avail + row * n_act : nullptr;
+    uint32_t c[4] = {off_lo, off_hi, (uint32_t)row, (uint32_t)(row >> 32)};
+    philox4x32_10(c, k0, k1);
+    const float u = (float)(c[0] >> 8) * 0x1p-24f;
+    int n_avail = 0, best = -1;
+    float qbest = 0.0f;
+    for (int i = 0; i < n_act; i++) {
+        if (av && !av[i]) continue;
+        n_avail++;
+        const float v = qr[i];
+        // the first available action seeds the maximum; a NaN seed yields to the first number
+        if (best < 0 || v > qbest || (qbest != qbest && v == v)) {
+            best = i;
+            qbest = v;
+        }
+    }
+    int a = best < 0 ? 0 : best;
+    if (u < epsilon && n_avail > 0) {
+        int k = (int)(((uint64_t)c[1] * (uint64_t)n_avail) >> 32);
+        for (int i = 0; i < n_act; i++) {
+            if (av && !av[i]) continue;
+            if (k-- == 0) {
+                a = i;
+                break;
+            }
+        }
+    }
+    actions[row] = (uint8_t)a;
+}
+
 __global__ void k_counter_add(uint64_t* __restrict__ c, uint64_t v) {
     if (threadIdx.x == 0) *c += v;
 }
@@ -155,6 +209,43 @@ int mdl_sample_actions_dev(const float* logits, int64_t n_rows, int32_t n_action
                        (uint32_t)(offset_add >> 32), offset_dev, actions, log_probs);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : rfail("mdl_sample_actions_dev: launch failed", e);
+}
+
+static int select_eps(const char* what, const float* q, const uint8_t* avail, int64_t n_rows, int32_t n_actions,
+                      float epsilon, uint64_t seed, uint64_t offset, const float* epsilon_dev,
+                      const uint64_t* offset_dev, uint8_t* actions, void* stream) {
+    char msg[96];
+    if (!q || !actions) {
+        snprintf(msg, sizeof msg, "%s: null argument", what);
+        return rfail(msg);
+    }
+    if (n_rows < 0 || n_actions < 1 || n_actions > 256) {
+        snprintf(msg, sizeof msg, "%s: bad sizes", what);
+        return rfail(msg);
+    }
+    if (n_rows == 0) return 0;
+    const int64_t blocks = (n_rows + 255) / 256;
+    hipLaunchKernelGGL(mdl::k_select_eps, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, q, avail, n_rows,
+                       (int)n_actions, epsilon, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)offset,
+                       (uint32_t)(offset >> 32), epsilon_dev, offset_dev, actions);
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return 0;
+    snprintf(msg, sizeof msg, "%s: launch failed", what);
+    return rfail(msg, e);
+}
+
+int mdl_select_actions_eps(const float* q, const uint8_t* avail, int64_t n_rows, int32_t n_actions, float epsilon,
+                           uint64_t seed, uint64_t offset, uint8_t* actions, void* stream) {
+    return select_eps("mdl_select_actions_eps", q, avail, n_rows, n_actions, epsilon, seed, offset, nullptr, nullptr,
+                      actions, stream);
+}
+
+int mdl_select_actions_eps_dev(const float* q, const uint8_t* avail, int64_t n_rows, int32_t n_actions,
+                               const float* epsilon_dev, uint64_t seed, const uint64_t* offset_dev,
+                               uint64_t offset_add, uint8_t* actions, void* stream) {
+    if (!epsilon_dev || !offset_dev) return rfail("mdl_select_actions_eps_dev: null argument");
+    return select_eps("mdl_select_actions_eps_dev", q, avail, n_rows, n_actions, 0.0f, seed, offset_add, epsilon_dev,
+                      offset_dev, actions, stream);
 }
 
 int mdl_counter_add(uint64_t* counter, uint64_t value, void* stream) {

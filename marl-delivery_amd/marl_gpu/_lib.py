@@ -78,6 +78,7 @@ SIGNATURES = {
     "mdl_tracker_clear": (C.c_int, [_vp, _vp, _i32, _vp]),
     "mdl_step": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "mdl_step_obs": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mdl_step_episode": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mdl_step_fused": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "mdl_step_floor": (C.c_int, [_vp, _i32, _vp]),
     "mdl_build_obs": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
@@ -97,6 +98,8 @@ SIGNATURES = {
     "mdl_load_state": (C.c_int, [_vp, _vp, C.c_int64, _vp]),
     "mdl_sample_actions": (C.c_int, [_vp, C.c_int64, _i32, C.c_uint64, C.c_uint64, _vp, _vp, _vp]),
     "mdl_sample_actions_dev": (C.c_int, [_vp, C.c_int64, _i32, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp]),
+    "mdl_select_actions_eps": (C.c_int, [_vp, _vp, C.c_int64, _i32, C.c_float, C.c_uint64, C.c_uint64, _vp, _vp]),
+    "mdl_select_actions_eps_dev": (C.c_int, [_vp, _vp, C.c_int64, _i32, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp]),
     "mdl_counter_add": (C.c_int, [_vp, C.c_uint64, _vp]),
     "mdl_gae": (C.c_int, [_vp, _vp, _vp, _vp, _i32, C.c_int64, C.c_float, C.c_float, _vp, _vp, _vp]),
     "mdl_read_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

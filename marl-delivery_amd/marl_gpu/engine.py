@@ -315,6 +315,56 @@ class BatchedEnv:
         # only the outputs written by this call (a cached dict's other entries would be stale)
         return out[0], out[1], out[2], {k: (v if k in which else None) for k, v in obs_out.items()}
 
+    def _check_mask(self, t, name):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+            raise TypeError(f"{name} must be a uint8 tensor")
+        if not t.is_cuda or t.get_device() != self.device.index or not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous on {self.device}")
+        if t.numel() < self.E:
+            raise ValueError(f"{name} holds {t.numel()} entries, needs {self.E}")
+
+    def step_episode(self, actions: torch.Tensor, active: torch.Tensor, action_format: str = "int", out=None,
+                     filled: torch.Tensor | None = None, obs_out: dict | None = None,
+                     which=("actor_map", "actor_vec", "critic_map", "critic_vec")):
+        """One transition of an episode batch (QMIX/trainer.py:363-511 steps only the envs whose
+        episode still runs): ``step(auto_reset=False)`` + ``build_obs`` for the envs whose byte of
+        ``active`` (uint8 [E] on the device, the caller's) is set, with no host round trip -- one
+        launch where ``step_obs`` is one.  A done env's byte is cleared on the device.  The other
+        envs are not touched: their r_env / r_shaped / done / ``filled`` are 0 and their rows of
+        ``obs_out`` are left unwritten.  Never resets.  Returns (r_env, r_shaped, done, obs dict);
+        ``filled`` (uint8 [E]) receives 1 for the envs that were stepped."""
+        n = self.E
+        if actions.dtype is not torch.uint8 or not actions.is_cuda or not actions.is_contiguous() \
+                or actions.get_device() != self._dev or actions.numel() != n * self.A:
+            actions = self._step_args(actions, n)
+        self._check_mask(active, "active")
+        if filled is not None:
+            self._check_mask(filled, "filled")
+        if out is None:
+            out = self._full_out
+            ptrs = (out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr())
+        else:
+            ptrs = self._out_ptrs(out, (n,))
+        if self._shape_run_end[0] < n:
+            raise ValueError("step_episode: the envs mix map shapes (build one engine per map shape)")
+        H, W = self.grids[int(self.env_map[0])].shape
+        if obs_out is None:
+            obs_out = self._obs_cache if getattr(self, "_obs_cache", None) is not None else self.obs_buffers(n, H, W)
+            self._obs_cache = obs_out
+        shapes = dict(actor_map=(n, self.A, 6, H, W), actor_vec=(n, self.A, self.actor_vec_dim),
+                      critic_map=(n, 4, H, W), critic_vec=(n, self.critic_vec_dim))
+        op = {}
+        for k in ("actor_map", "actor_vec", "critic_map", "critic_vec"):
+            t = obs_out.get(k) if k in which else None
+            if t is not None:
+                self._check_obs_out(t, k, shapes[k])
+            op[k] = None if t is None else t.data_ptr()
+        check(lib().mdl_step_episode(self._h, actions.data_ptr(), ACTION_FORMATS[action_format], active.data_ptr(),
+                                     ptrs[0], ptrs[1], ptrs[2], ptr(filled), op["actor_map"], op["actor_vec"],
+                                     op["critic_map"], op["critic_vec"], _raw_stream(self._dev)), "mdl_step_episode")
+        self._keep = (None, actions)
+        return out[0], out[1], out[2], {k: (v if k in which else None) for k, v in obs_out.items()}
+
     def step_fused(self, actions: torch.Tensor, env_ids=None, auto_reset: bool = True, action_format: str = "int",
                    out=None):
         """Bench mode: K consecutive steps in one launch.

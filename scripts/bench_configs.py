@@ -10,6 +10,8 @@
   --config rollout / rollout_graph   MAPPO rollout on the device
   --config alt      IDQ/qmix featurizers (§8(f)2)
   --config greedy   batched greedy baseline (§8(f)3)
+  --qmix            QMIX episode collection: the masked step against the full step, and one collector
+                    step against the host-driven subset loop
 
 Prints one JSON line per config with per-kernel HIP-event times and the
 algorithmic-bytes roofline of SURVEY.md §8(d).
@@ -243,6 +245,148 @@ def run_greedy(steps):
     env.close()
 
 
+def _graph_of(fn):
+    """fn() captured once as a hipGraph (after one eager call)."""
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.stream(s):
+        fn()
+        torch.cuda.synchronize()
+        with torch.cuda.graph(g, stream=s):
+            fn()
+    torch.cuda.synchronize()
+    return g
+
+
+def _replay_us(g, reps, per):
+    g.replay()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    for _ in range(reps):
+        g.replay()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / (reps * per) * 1e3
+
+
+def run_qmix(steps):
+    """QMIX episode collection ("QMIX episode collection").
+
+    1. The masked step against the full step: ``step_episode`` with every env active against
+       ``step_obs(auto_reset=False)`` on the same engine in the same run, hipGraph-replayed, five
+       repeats each, interleaved.  Both graphs are [reset, mask fill, G steps], so no env ends inside
+       one and the fixed part is the same on both sides.  map1, A=5, P=20; 16,384 envs and 4.
+    2. One collector step (``select_actions_eps`` + ``step_episode``, half of the envs inactive)
+       against the host-driven subset loop it replaces (done mask read back, id list built on the
+       host and uploaded, action rows gathered, ``step(env_ids=...)``, ``build_obs()``); 4 and 4,096 envs.
+    """
+    import marl_gpu
+    import marl_gpu.qmix_rollout as Q
+    from marl_gpu.maps import grid_array, load_map, map_path
+    g1 = grid_array(load_map(map_path("map1.txt")))
+    A, P, T, G = 5, 20, 500, 50
+    dev = torch.device("cuda", 0)
+    gen = torch.Generator(device=dev).manual_seed(0)
+    reps = max(2, steps // G)
+    for E in (16384, 4):
+        env = marl_gpu.BatchedEnv(g1, E, A, P, T, seed=42, tracker="fresh", shaping="qmix")
+        acts = torch.randint(0, 15, (G, E, A), generator=gen, device=dev, dtype=torch.int32).to(torch.uint8)
+        bufs = env.obs_buffers()
+        out = (torch.zeros(E, dtype=torch.float64, device=dev), torch.zeros(E, dtype=torch.float32, device=dev),
+               torch.zeros(E, dtype=torch.uint8, device=dev))
+        active = torch.ones(E, dtype=torch.uint8, device=dev)
+        filled = torch.zeros(E, dtype=torch.uint8, device=dev)
+
+        def full():
+            env.reset()
+            active.fill_(1)
+            for k in range(G):
+                env.step_obs(acts[k], auto_reset=False, out=out, obs_out=bufs)
+
+        def masked():
+            env.reset()
+            active.fill_(1)
+            for k in range(G):
+                env.step_episode(acts[k], active, out=out, filled=filled, obs_out=bufs)
+
+        gf, gm = _graph_of(full), _graph_of(masked)
+        tf, tm = [], []
+        for _ in range(5):
+            tf.append(_replay_us(gf, reps, G))
+            tm.append(_replay_us(gm, reps, G))
+        assert bool(active.all()), "an env ended inside the measured graph"
+        print(json.dumps({"config": "qmix_masked_step", "envs": E, "agents": A, "packages": P, "graph_steps": G,
+                          "replays": reps, "step_obs_us": tf, "step_episode_us": tm,
+                          "step_obs_spread_us": max(tf) - min(tf), "median_gap_us": float(np.median(tm) - np.median(tf)),
+                          "kernels": [env.step_kernel_name(with_obs=True), "mdl::k_step_episode (same shapes)"],
+                          "note": "us per step of [reset, mask fill, 50 steps] graphs, every env active"}), flush=True)
+        env.close()
+
+    for E in (4, 4096):
+        env = marl_gpu.BatchedEnv(g1, E, A, P, T, seed=42, tracker="fresh", shaping="qmix")
+        ref = marl_gpu.BatchedEnv(g1, E, A, P, T, seed=42, tracker="fresh", shaping="qmix")
+        q = torch.randn(G, E * A, 15, generator=gen, device=dev)
+        half = (torch.arange(E, device=dev) % 2 == 0).to(torch.uint8)
+        u = torch.zeros((E, A), dtype=torch.uint8, device=dev)
+        bufs = env.obs_buffers()
+        out = (torch.zeros(E, dtype=torch.float64, device=dev), torch.zeros(E, dtype=torch.float32, device=dev),
+               torch.zeros(E, dtype=torch.uint8, device=dev))
+        active = torch.ones(E, dtype=torch.uint8, device=dev)
+        filled = torch.zeros(E, dtype=torch.uint8, device=dev)
+
+        def coll_step(k):
+            Q.select_actions_eps(q[k % G], 0.2, 1, k, out=u.view(-1))
+            env.step_episode(u, active, out=out, filled=filled, obs_out=bufs)
+
+        def coll_graph():
+            env.reset()
+            active.copy_(half)
+            for k in range(G):
+                coll_step(k)
+
+        env.reset()
+        active.copy_(half)
+        for k in range(5):
+            coll_step(k)
+        env.reset()
+        active.copy_(half)
+        coll_eager = timed(coll_step, G)
+        coll_g = _replay_us(_graph_of(coll_graph), reps, G)
+
+        rbufs = ref.obs_buffers()
+        state = {"done": torch.zeros(E, dtype=torch.uint8, device=dev), "mask": half.cpu().numpy().astype(bool)}
+
+        def host_step(k):
+            # the parent's path (tests/test_gpu_parity.py::test_qmix_rollout_golden): one round trip to
+            # learn which envs finished, a host-built id list, the subset step, the observation build
+            state["mask"] &= ~state["done"].cpu().numpy().astype(bool)
+            idx = np.nonzero(state["mask"])[0]
+            ids = torch.from_numpy(idx.astype(np.int32)).to(dev)
+            a = q[k % G].view(E, A, 15)[:, :, 0].gt(0).to(torch.uint8)[ids.long()].contiguous()   # stand-in actions
+            _, _, dn = ref.step(a, env_ids=ids, auto_reset=False)
+            state["done"].zero_()
+            state["done"][ids.long()] = dn
+            ref.build_obs(out=rbufs)
+
+        ref.reset()
+        for k in range(5):   # torch's indexing kernels and the copy paths, once
+            host_step(k)
+        ref.reset()
+        state["done"].zero_()
+        state["mask"] = half.cpu().numpy().astype(bool)
+        host_us = timed(host_step, G)
+        print(json.dumps({"config": "qmix_collector_step", "envs": E, "agents": A, "active_fraction": 0.5,
+                          "collector_step_graph_us": coll_g, "collector_step_eager_us": coll_eager,
+                          "host_loop_step_us": host_us,
+                          "launches": {"collector": "2 kernels (k_select_eps, k_step_episode), no copy, no sync",
+                                       "host_loop": "k_step (subset) + k_obs_small + the torch gather/scatter kernels, "
+                                                    "1 D2H + 1 H2D copy, 1 host sync per step"}}), flush=True)
+        env.close()
+        ref.close()
+
+
 def run_config1(seconds=5.0):
     """BASELINE.json configs[0]: map1, 5 agents, ONE env, a random agent driving the dict
     API (randomagent.py: np.random.choice over moves and ops per robot) -- plumbing, not a
@@ -278,8 +422,12 @@ def main():
     ap.add_argument("--config", default="3,3b,4,5")
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--qmix", action="store_true", help="the QMIX episode-collection measurements only")
     a = ap.parse_args()
     torch.cuda.set_device(0)
+    if a.qmix:
+        run_qmix(a.steps)
+        return
     for c in a.config.split(","):
         if c == "1":
             run_config1()
