@@ -399,6 +399,8 @@ struct MailArgs {
     uint8_t codes[MAIL_INLINE_CODES];
 };
 
+#include "mdl_step_common.hpp"
+
 // The step kernel's body.  OBS (NCH = 1, A <= 8, k_obs_small's configurations): after the
 // write-back the wave builds the env's observations of the new state from the registers the
 // step leaves (robots on lanes < A, package j on lane j), as MAPPO/trainer.py:229-286 does
@@ -619,9 +621,7 @@ __device__ __forceinline__ void step_body(const uint32_t* __restrict__ rob_pre, 
         uint64_t wvm[NCH], anyw = 0;
 #pragma unroll
         for (int c = 0; c < NCH; c++) {
-            const uint32_t f = ps0[c];
-            const bool waiting = STALE ? ((f & PS_PRESENT) && !(f & PS_TRANSIT)) : ((f & PS_STATUS) == ST_WAITING);
-            wv[c] = waiting && pk_st(td[c]) <= t0;
+            wv[c] = trk_waiting<STALE>(ps0[c], td[c], t0);
             stc[c] = pk_start(td[c]);
             klo[c] = wv[c] ? (tq[c] << 10) | (uint32_t)(c * WAVE + lane) : 0xffffffffu;
             wvm[c] = ballot(wv[c]);
@@ -635,15 +635,7 @@ __device__ __forceinline__ void step_body(const uint32_t* __restrict__ rob_pre, 
         // winner = lowest-index mover into the cell: the reference's restart-from-0
         // loop, checked against the oracle's literal restatement.
         const int pcell = cell, pcarry = carry;
-        // bits 1..4 of vmask only: S / other moves never move; L -256, R +256, U -1, D +1
-        // the cell delta of each move code from one 64-bit table of 10-bit entries
-        // (S 0, L -256, R +256, U -1, D +1, other 0), masked by the move's validity bit
-        constexpr uint64_t DTAB = (uint64_t)(0x3ffu & (uint32_t)-256) << 10 | (uint64_t)256 << 20 |
-                                  (uint64_t)(0x3ffu & (uint32_t)-1) << 30 | (uint64_t)1 << 40;
-        const int dtab = __builtin_amdgcn_sbfe((int)(uint32_t)(DTAB >> (10 * mv)), 0, 10);
-        const int vok = __builtin_amdgcn_sbfe((int)vmask, mv, 1);   // 0 or -1
-        const int dlt = dtab & vok;
-        const int prop = cell + (int)(lmask(act) & (uint32_t)dlt);   // a vector mask: no exec-masked block
+        const int prop = move_proposal(act, cell, vmask, mv);
         const bool mover = !(MDL_ABLATE & 4) && act && prop != cell;
         const uint64_t movers = ballot(mover);
         // the proposed cell's move-validity bits, fetched now (every mover) so the load
@@ -1279,8 +1271,7 @@ __global__ __launch_bounds__(256) void k_episode_end(uint8_t* __restrict__ activ
     if (filled[e] && done[e]) active[e] = 0;
 }
 
-#include "mdl_step_rows.hpp"
-#include "mdl_step_halves.hpp"
+#include "mdl_step_multi.hpp"
 
 // ------------------------------------------------------------- observations
 // Tracker slots staged in LDS for the feature builders (random access by id).
