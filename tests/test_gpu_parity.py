@@ -320,8 +320,9 @@ def test_vs_oracle_rows_layout(mapname, A, P, T):
                                            ("map1.txt", 7, 30, 40), ("map2.txt", 5, 100, 40),
                                            ("map2.txt", 5, 200, 40), ("map3.txt", 9, 70, 40)])
 def test_vs_oracle_robot_counts(mapname, A, P, T):
-    """Every step-kernel specialisation: A == 5 exactly (P <= 128), A <= 8 with the
-    robot count at run time (incl. numpy's 8-partial sum at A == 8), the general form."""
+    """The robot-count forms of the per-step kernel at 32 envs, stale tracker: A == 5 exactly
+    (P <= 128), A <= 8 with the robot count at run time (incl. numpy's 8-partial sum at A == 8), the
+    general form.  Every instantiation of every step kernel, one by one: test_gpu_step_matrix.py."""
     _oracle_compare(mapname, 32, A, P, T, 300 + A, 90, "mappo")
 
 

@@ -313,6 +313,94 @@ def test_halves_step_kernels_have_no_scratch(tmp_path):
         assert res[n]["vgpr_count"] <= (72 if "k_step_halvesILb1ELi3E" in n else 80), (n, res[n])
 
 
+# Matrix symbols whose case is left out of tests/step_matrix.py because it faulted on the GPU with the
+# cause not found; each entry needs a comment naming the fault.  Empty otherwise.
+STEP_MATRIX_EXCLUDED = set()
+
+
+def _mangled_prefix(symbol):
+    """Itanium mangling of a step kernel's name and template arguments (bools and ints only)."""
+    name, args = symbol[len("mdl::"):-1].split("<")
+    targs = "".join(f"Lb{int(a == 'true')}E" if a in ("true", "false") else f"Li{int(a)}E" for a in args.split(", "))
+    return f"_ZN3mdl{len(name)}{name}I{targs}EE"
+
+
+@pytest.mark.skipif(not os.path.exists(f"{LLVM_BIN}/llvm-readelf"), reason="ROCm LLVM tools absent")
+def test_step_matrix_lists_every_step_kernel(tmp_path):
+    """The step kernels in the library's gfx950 code objects (k_step_floor, the empty launch-floor kernel,
+    aside) are exactly the symbols of tests/step_matrix.py, each of which test_gpu_step_matrix.py steps
+    against the oracle: 28 plain, 28 K-step fused, 20 mailbox, 4 step + observations, 4 episode, 8 rows,
+    4 halves.  A kernel added to the dispatch without a matrix entry, or an entry the library no
+    longer holds, fails here."""
+    from collections import Counter
+
+    import step_matrix
+    from marl_gpu import _lib
+    res = _kernel_resources(_lib.LIB_PATH, tmp_path)
+    built = sorted(n for n in res if "k_step" in n and "k_step_floor" not in n)
+    cxxfilt = f"{LLVM_BIN}/llvm-cxxfilt"
+    if os.path.exists(cxxfilt):
+        out = subprocess.run([cxxfilt] + built, capture_output=True, text=True, check=True).stdout.split("\n")
+        have = [re.sub(r"^void ", "", d.split("(")[0]) for d in out if d]   # void mdl::k_step<...>(unsigned int const*, ...
+    else:   # no demangler: match each symbol's mangled name + template arguments, as the tests above do
+        by_prefix = {_mangled_prefix(s): s for s in step_matrix.SYMBOLS}
+        have = [next((s for p, s in by_prefix.items() if n.startswith(p)), n) for n in built]
+    assert len(have) == len(set(have)) == len(built), Counter(have).most_common(3)
+    want = Counter(step_matrix.SYMBOLS)
+    assert max(want.values()) == 1, [s for s, k in want.items() if k > 1]
+    assert not (STEP_MATRIX_EXCLUDED & set(want)), "an excluded symbol has a matrix entry again: drop the exclusion"
+    assert set(have) - STEP_MATRIX_EXCLUDED == set(want), (sorted(set(have) - STEP_MATRIX_EXCLUDED - set(want)),
+                                                            sorted(set(want) - set(have)))
+    kinds = Counter(c.variant for c in step_matrix.CASES)
+    if not STEP_MATRIX_EXCLUDED:
+        assert len(want) == 96 and kinds == dict(plain=28, fused=28, mail=20, obs=4, episode=4, rows=8, halves=4)
+    for s in step_matrix.SYMBOLS:   # the mangling rule the fallback uses holds for every symbol
+        assert any(n.startswith(_mangled_prefix(s)) for n in built), s
+
+
+def test_step_matrix_shapes_select_their_symbols():
+    """Each matrix entry's shape selects its symbol by the dispatch rule (restated here; the engine
+    itself names only the plain and observation launches, which the GPU test asks it for), fits its
+    map, and the table as a whole runs both edges of every package-chunk class, the mailbox path
+    past 256 action bytes in both tracker modes and id subsets."""
+    import step_matrix
+    from golden_io import grid
+    edges = {1: (1, 64), 2: (65, 128), 4: (129, 256), 8: (257, 512), 16: (513, 1024)}
+    seen = set()
+    for c in step_matrix.CASES:
+        st = {"mappo": "true", "fresh": "false"}[c.tracker]
+        nch = next(k for k, (_, hi) in edges.items() if c.P <= hi)
+        assert c.P in edges[nch] or c.variant in ("rows", "halves"), c
+        assert int((grid(c.map) == 0).sum()) >= c.A, c
+        assert c.T == 25 and c.E == {"rows": 6, "halves": 3}.get(c.variant, 29 if c.E == 29 else 5), c
+        if c.variant in ("plain", "fused"):
+            au = (5 if c.A == 5 else 16 if c.A == 16 else 8 if c.A <= 8 else 0) if nch <= 2 else (8 if c.A <= 8 else 0)
+            assert c.A in {5: (5,), 16: (16,), 8: (1, 5, 8), 0: (9, 15, 16, 17, 64)}[au], c
+            want = f"mdl::k_step<{st}, {nch}, {'true' if c.variant == 'fused' else 'false'}, {au}>"
+            seen.add((c.variant, st, c.P))
+        elif c.variant == "mail":
+            want = f"mdl::k_step_mail<{st}, {nch}, {8 if c.A <= 8 else 0}>"
+            seen.add((c.variant, st, c.P))
+        elif c.variant in ("obs", "episode"):
+            assert c.A <= 8 and nch == 1, c
+            want = f"mdl::k_step_{c.variant}<{st}, {5 if c.A == 5 else 8}>"
+        elif c.variant == "rows":
+            assert c.A <= 8 and c.P in (1, 47, 48, 64), c
+            want = f"mdl::k_step_rows<{st}, {5 if c.A == 5 else 8}, 4, {3 if c.P >= 48 else 0}>"
+        else:
+            assert c.variant == "halves" and c.A == 16 and c.P in (1, 95, 96, 128), c
+            want = f"mdl::k_step_halves<{st}, {3 if c.P >= 96 else 0}>"
+        assert c.symbol == want, (c, want)
+    for v in ("plain", "fused", "mail"):       # both edges of every class, in both tracker modes
+        for st in ("true", "false"):
+            for lo, hi in edges.values():
+                assert (v, st, lo) in seen and (v, st, hi) in seen, (v, st, lo, hi)
+    mail = [c for c in step_matrix.CASES if c.variant == "mail"]
+    assert {c.tracker for c in mail if c.E * c.A > 256} == {"mappo", "fresh"}
+    assert sum(c.subset for c in mail) >= 2
+    assert not any(c.subset for c in step_matrix.CASES if c.variant != "mail")
+
+
 def test_bench_step_layout_flag():
     """bench.py --step-layout reaches BatchedEnv (MdlConfig.step_layout); auto is the default."""
     bench = _bench_module()
