@@ -182,6 +182,30 @@ int mdl_views_idq_reward(MdlEngine* eng, const int32_t* prev_views, const int64_
                          const int32_t* cur, const int64_t* cur_offsets, const uint8_t* ops, const int64_t* op_offsets,
                          int32_t ops_are_ints, int32_t n, double* out, void* stream);
 
+/* One IDQ transition's device side, after the step (DQNTrainer.run_episode, IDQ/trainer.py:286-311):
+ * reward_shaping (IDQ/networks.py:228-349) per agent and convert_state of the next state, from engine
+ * state, for all E envs (one map shape), row e = env e.  reward_shaping reads the state and the tracker
+ * from BEFORE the step, which mdl_step has already replaced; what it reads of them is kept in a
+ * caller-owned pre-record: a DEVICE buffer of mdl_alt_pre_bytes bytes, 16-byte aligned -- per (env,
+ * agent) 16 bytes (the robot word; whether a tracked, waiting, started package starts on the agent's
+ * cell; the carried tracked package's target cell and deadline), then int32 t per env.  The engine
+ * keeps no hidden state for it: checkpoints, mdl_reset and the step entry points are unaffected.
+ *   row_mask != NULL and row_mask[e] == 0: r_idq[e][0..A) = 0 (where actions != NULL); env e's rows
+ *     of idq_obs / qmix_state and of the pre-record are NOT written.
+ *   otherwise: r_idq[e][a] (f64 [E][A], reward_shaping's accumulation order) from pre[e], the new
+ *     robot words, the new t and the op of actions[e][a] (uint8 [E][A], decoded by action_format as
+ *     mdl_step does; ops_are_ints = 0 hands over op -1 -- IDQ/trainer.py passes string ops, so only
+ *     the stay penalty fires); then pre[e] = the record of the new state, and the observations of the
+ *     new state as mdl_build_obs_alt writes them (idq_obs f32 [E][A][6][H][W], qmix_state f32
+ *     [E][7][out_h][out_w]; either may be NULL).
+ *   actions == NULL ("begin", after a reset): no reward, only the pre-record and the observations.
+ * Per step: mdl_step_episode(actions, active, ..., filled, no observations), then
+ * mdl_alt_transition(actions, ..., row_mask = filled, ...).  One launch; captures into a hipGraph. */
+int mdl_alt_pre_bytes(const MdlEngine* eng, int64_t* bytes);
+int mdl_alt_transition(MdlEngine* eng, const uint8_t* actions, int32_t action_format, int32_t ops_are_ints,
+                       const uint8_t* row_mask, void* pre, double* r_idq, float* idq_obs, float* qmix_state,
+                       int32_t out_h, int32_t out_w, void* stream);
+
 /* ---- greedy baseline: greedyagent.py batched on the device ----
  * mdl_greedy_init = GreedyAgents() + init_agents(state) for the listed envs (call it right
  * after their reset, as evaluation.py:29-35 does); the first call also builds run_bfs's
@@ -318,6 +342,26 @@ int mdl_select_actions_eps_dev(const float* q, const uint8_t* avail, int64_t n_r
 
 /* *counter += value on the device (stream-ordered; advances offset_dev inside a graph). */
 int mdl_counter_add(uint64_t* counter, uint64_t value, void* stream);
+
+/* One step's appends to IDQ's per-transition replay buffer (the buffer.add calls of
+ * IDQ/trainer.py:304-311 on ReplayBuffer.add, IDQ/networks.py:63-79), needing no engine: for every env
+ * with filled[e] != 0, in env order, and every agent a in order, one row (obs[e][a], actions[e][a],
+ * reward[e][a], next_obs[e][a], done[e]) goes to ring slot ptr; then ptr = (ptr + 1) % capacity and
+ * size = min(size + 1, capacity).  All pointers DEVICE: filled, done uint8 [E]; obs, next_obs f32
+ * [E][A][row_floats]; actions uint8 [E][A]; reward f64 [E][A] (stored rounded once to float32, as the
+ * reference's float32 array does); cursor int64 [2] = (ptr, size), read and advanced on the device (no
+ * host round trip); the ring: ring_obs, ring_next_obs f32 [capacity][row_floats], ring_action int64,
+ * ring_reward f32, ring_done uint8 [capacity]; rank_scratch int32 [E + 3] (the envs' ranks among the
+ * filled ones, then the filled count and the step's first slot).  Two launches: a one-workgroup prefix
+ * sum over `filled` that also advances the cursor, and the copy, one wave per filled env (16-byte
+ * vectors where row_floats % 4 == 0 and the four row pointers are 16-byte aligned).  A step with more
+ * rows than `capacity` leaves its last `capacity` rows, each written once, as the sequential adds do.
+ * E <= MDL_REPLAY_MAX_ENVS (the prefix sum is one workgroup's loop); a larger E is refused. */
+#define MDL_REPLAY_MAX_ENVS 65536
+int mdl_replay_append(const uint8_t* filled, int32_t E, int32_t A, int64_t row_floats, const float* obs,
+                      const float* next_obs, const uint8_t* actions, const double* reward, const uint8_t* done,
+                      int64_t capacity, int64_t* cursor, float* ring_obs, float* ring_next_obs, int64_t* ring_action,
+                      float* ring_reward, uint8_t* ring_done, int32_t* rank_scratch, void* stream);
 
 /* Generalised advantage estimation exactly as MAPPO/trainer.py:266-276 computes it in float32
  * (same operation order): rewards, values, dones [T][n] (dones uint8), next_value [n];

@@ -237,34 +237,29 @@ __device__ inline void alt_emit_qmix(const uint8_t* grid, int H, int W, const Al
     });
 }
 
+// What reward_shaping reads of the tracker from before the step, per agent:
+//   avail     a tracked, waiting, started package starts on the agent's previous cell
+//   tracked   the previously carried id is in the tracker; then target / deadline are its
+struct IdqTrkFacts {
+    bool avail, tracked;
+    int target, deadline;
+};
+
 // reward_shaping for the agent on this lane (fp64, the reference's accumulation order).
 // op < 0 means the reference was handed string ops (IDQ/trainer.py): no op branch fires.
-template <class Trk>
-__device__ inline double idq_reward(const Trk& trk, int prev_cell, int prev_carry, int cur_cell, int cur_carry, int op,
-                                    int t_prev, int t_cur) {
+__device__ inline double idq_reward_facts(int prev_cell, int prev_carry, int cur_cell, int cur_carry, int op,
+                                          int t_cur, const IdqTrkFacts& f) {
     double r = 0.0;
     if (prev_cell == cur_cell) r = r + -0.1;                           // SHAPING_STAY_PENALTY
     if (op == 1) {
         if (prev_carry == 0 && cur_carry != 0) r = r + 2.0;            // SHAPING_SUCCESSFUL_PICKUP_BONUS
         else if (prev_carry != 0) r = r + -0.1;                        // SHAPING_WASTED_PICKUP_PENALTY
-        else {
-            bool avail = false;
-            for (int j = 0; j < trk.count() && !avail; j++) {
-                if (!trk.present(j) || trk.in_transit(j)) continue;
-                const uint64_t d = trk.data(j);
-                avail = pk_start(d) == prev_cell && pk_st(d) <= t_prev;
-            }
-            if (!avail) r = r + -0.1;
-        }
+        else if (!f.avail) r = r + -0.1;
     } else if (op == 2) {
         if (prev_carry != 0 && cur_carry == 0) {
-            const int sl = trk.slot_of(prev_carry);
-            if (sl >= 0) {
-                const uint64_t d = trk.data(sl);
-                if (cur_cell == pk_target(d)) {
-                    r = r + 10.0;                                        // SHAPING_SUCCESSFUL_DELIVERY_BONUS
-                    if (t_cur > pk_dl(d)) r = r + -5.0;                  // SHAPING_LATE_DELIVERY_PENALTY
-                }
+            if (f.tracked && cur_cell == f.target) {
+                r = r + 10.0;                                            // SHAPING_SUCCESSFUL_DELIVERY_BONUS
+                if (t_cur > f.deadline) r = r + -5.0;                    // SHAPING_LATE_DELIVERY_PENALTY
             }
         } else if (prev_carry == 0) {
             r = r + 0.0;                                                 // SHAPING_WASTED_DROP_PENALTY
@@ -272,5 +267,41 @@ __device__ inline double idq_reward(const Trk& trk, int prev_cell, int prev_carr
     }
     return r;
 }
+
+// The same from the tracker itself (k_views_idq_reward): the facts are looked up only
+// where the reward reads them.
+template <class Trk>
+__device__ inline double idq_reward(const Trk& trk, int prev_cell, int prev_carry, int cur_cell, int cur_carry, int op,
+                                    int t_prev, int t_cur) {
+    IdqTrkFacts f{false, false, 0, 0};
+    if (op == 1 && prev_carry == 0 && cur_carry == 0) {
+        for (int j = 0; j < trk.count() && !f.avail; j++) {
+            if (!trk.present(j) || trk.in_transit(j)) continue;
+            const uint64_t d = trk.data(j);
+            f.avail = pk_start(d) == prev_cell && pk_st(d) <= t_prev;
+        }
+    } else if (op == 2 && prev_carry != 0 && cur_carry == 0) {
+        const int sl = trk.slot_of(prev_carry);
+        if (sl >= 0) {
+            const uint64_t d = trk.data(sl);
+            f = IdqTrkFacts{false, true, pk_target(d), pk_dl(d)};
+        }
+    }
+    return idq_reward_facts(prev_cell, prev_carry, cur_cell, cur_carry, op, t_cur, f);
+}
+
+// The caller-owned pre-record of mdl_alt_transition: one entry per (env, agent) of what
+// reward_shaping reads of the state and the tracker from before the step, then the envs' t.
+struct AltPre {
+    uint32_t rob;       // the robot word (rob_cell / rob_carry)
+    uint32_t flags;     // ALT_PRE_AVAIL | ALT_PRE_TRACKED
+    int32_t target;     // packed target cell of the carried, tracked package
+    int32_t deadline;   // its deadline
+};
+static_assert(sizeof(AltPre) == 16, "AltPre is one 16-byte store");
+enum : uint32_t { ALT_PRE_AVAIL = 1u, ALT_PRE_TRACKED = 2u };
+
+__host__ __device__ inline size_t alt_pre_t_off(int E, int A) { return (size_t)E * A * sizeof(AltPre); }
+__host__ __device__ inline size_t alt_pre_bytes(int E, int A) { return alt_pre_t_off(E, A) + (size_t)E * sizeof(int32_t); }
 
 }  // namespace mdl

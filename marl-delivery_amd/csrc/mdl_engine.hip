@@ -1230,6 +1230,35 @@ int mdl_build_obs_alt(MdlEngine* eng, int32_t env_begin, int32_t n, float* idq_o
     return 0;
 }
 
+int mdl_alt_pre_bytes(const MdlEngine* eng, int64_t* bytes) {
+    if (!eng || !bytes) return fail("mdl_alt_pre_bytes: null argument");
+    *bytes = (int64_t)mdl::alt_pre_size(eng->p.E, eng->p.A);
+    return 0;
+}
+
+int mdl_alt_transition(MdlEngine* eng, const uint8_t* actions, int32_t action_format, int32_t ops_are_ints,
+                       const uint8_t* row_mask, void* pre, double* r_idq, float* idq_obs, float* qmix_state,
+                       int32_t out_h, int32_t out_w, void* stream) {
+    if (!eng || !pre) return fail("mdl_alt_transition: null argument");
+    if (actions && !r_idq) return fail("mdl_alt_transition: actions without r_idq");
+    if (((uintptr_t)pre & 15) != 0) return fail("mdl_alt_transition: pre must be 16-byte aligned");
+    if (actions && action_format != MDL_ACTION_TRAINER_INT && action_format != MDL_ACTION_CODES)
+        return fail("mdl_alt_transition: unknown action_format %d", action_format);
+    if (qmix_state && (out_h < 1 || out_w < 1 || out_h > 4096 || out_w > 4096))
+        return fail("mdl_alt_transition: bad state tensor shape (%d, %d)", out_h, out_w);
+    const int E = eng->p.E;
+    if (eng->shape_run_end[0] < E)
+        return fail("mdl_alt_transition: the envs mix map shapes (same-shape run ends at %d)", eng->shape_run_end[0]);
+    const size_t lds = mdl::alt_obs_lds(eng->p.P, eng->maxHW);
+    const int wpb = waves_per_block(lds);
+    if (wpb < 1) return fail("mdl_alt_transition: needs %zu bytes of LDS per env", lds);
+    DeviceGuard dg(eng->device);
+    HIPCHK(mdl::launch_alt_transition(eng->p, actions, action_format, ops_are_ints, row_mask, pre,
+                                      actions ? r_idq : nullptr, idq_obs, qmix_state, out_h, out_w, wpb, lds,
+                                      (hipStream_t)stream));
+    return 0;
+}
+
 int mdl_views_alt_features(MdlEngine* eng, const int32_t* views, const int64_t* offsets, int32_t n_views,
                            int32_t max_slots, const int32_t* agent_idx, float* idq_obs, float* qmix_state,
                            int32_t out_h, int32_t out_w, void* stream) {

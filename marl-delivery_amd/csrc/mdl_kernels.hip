@@ -1636,6 +1636,92 @@ __global__ __launch_bounds__(256) void k_alt_obs(DevParams p, int env_begin, int
     }
 }
 
+// mdl_alt_transition: one IDQ transition's device side for the envs `mask` marks, after their step
+// (DQNTrainer.run_episode, IDQ/trainer.py:286-311): reward_shaping (IDQ/networks.py:228-349) from the
+// caller's pre-record of the state and tracker before the step, the pre-record of the new state,
+// and k_alt_obs's observations of it into row e.  acts == NULL ("begin"): no reward.
+template <bool STALE>
+__global__ __launch_bounds__(256) void k_alt_transition(DevParams p, const uint8_t* __restrict__ acts, int fmt,
+                                                        int ops_are_ints, const uint8_t* __restrict__ mask,
+                                                        AltPre* __restrict__ pre, int32_t* __restrict__ pre_t,
+                                                        double* __restrict__ r_idq, float* __restrict__ idq,
+                                                        float* __restrict__ qst, int oh, int ow, int wpb,
+                                                        int lds_stride) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int wave = wave_id();
+    const int lane = lane_id();
+    const int e = blockIdx.x * wpb + wave;
+    if (wave >= wpb || e >= p.E) return;
+    const int A = p.A, P = p.P;
+    const bool act = lane < A;
+    const size_t ra = (size_t)e * A + lane;
+    if (mask && !mask[e]) {   // row mask: zero rewards, every other row of env e stays unwritten
+        if (acts && act) r_idq[ra] = 0.0;
+        return;
+    }
+    unsigned char* base = smem + (size_t)wave * lds_stride;
+    ObsLdsPre S = obs_pre_carve(base, P);
+    const MapDesc md = p.maps[p.env_map ? p.env_map[e] : 0];
+    const int H = md.H, W = md.W;
+    AltLds L = alt_carve(base + obs_pre_bytes(P), H * W);
+    const uint32_t rv = act ? p.rob[ra] : 0u;
+    const int cell = rob_cell(rv), carry = rob_carry(rv);
+    const int t = p.es[e].t;
+    if (acts && act) {
+        const AltPre q = pre[ra];
+        int mv, op;
+        decode_action(acts[ra], fmt, mv, op);
+        const IdqTrkFacts f{(q.flags & ALT_PRE_AVAIL) != 0, (q.flags & ALT_PRE_TRACKED) != 0, q.target, q.deadline};
+        r_idq[ra] = idq_reward_facts(rob_cell(q.rob), rob_carry(q.rob), cell, carry, ops_are_ints ? op : -1, t, f);
+    }
+    for (int j = lane; j < P; j += WAVE) {   // the package table and tracker, as k_alt_obs loads them
+        const size_t g = (size_t)e * P + j;
+        const uint64_t d = p.pkg[g];
+        const uint32_t f = p.pstate[g];
+        S.pk[j] = d;
+        S.ps[j] = (uint8_t)(f & PS_FLAGS);
+        if (STALE) {
+            const bool sv = (f & PS_SURVIVOR) != 0;
+            S.td[j] = sv ? p.trk[g] : d;
+            S.tq[j] = sv ? f >> PS_RANK_SHIFT : ORD_EPISODE + (uint32_t)j;
+        }
+    }
+    wave_sync();
+    const uint8_t* grid = p.grids + md.grid_off;
+    float* idq_e = idq ? idq + (size_t)e * A * 6 * H * W : nullptr;
+    float* qst_e = qst ? qst + (size_t)e * 7 * oh * ow : nullptr;
+    const bool fast = (H * W) % 4 == 0 && oh == H && ow == W && (((uintptr_t)idq_e | (uintptr_t)qst_e) & 15) == 0;
+    auto run = [&](const auto& trk) {
+        alt_prepare(trk, H * W, W, A, t, cell, carry, L);
+        if (act) {   // the record of this state: what the next step's reward reads
+            AltPre n{rv, L.urg[cell_r(cell) * W + cell_c(cell)] >= 0.0f ? ALT_PRE_AVAIL : 0u, 0, 0};
+            const int sl = carry != 0 ? trk.slot_of(carry) : -1;
+            if (sl >= 0) {
+                const uint64_t d = trk.data(sl);
+                n.flags |= ALT_PRE_TRACKED;
+                n.target = pk_target(d);
+                n.deadline = pk_dl(d);
+            }
+            pre[ra] = n;
+        }
+        if (lane == 0) pre_t[e] = t;   // the record's time step (the reward itself reads only `avail`, taken at it)
+        if (fast) {
+            alt_bits(p.gridbits + md.bits_off, H * W, L);
+            alt_emit_fast(trk, H, W, L, cell, carry, A, idq_e, qst_e);
+            return;
+        }
+        if (idq) alt_emit_idq(trk, grid, H, W, L, cell, carry, 0, A, true, idq_e);
+        if (qst) alt_emit_qmix(grid, H, W, L, oh, ow, qst_e);
+    };
+    if (STALE) {
+        TrkStale trk{S.ps, S.td, S.tq, P};
+        run(trk);
+    } else {
+        TrkFresh trk{S.pk, S.ps, P};
+        run(trk);
+    }
+}
+
 // The same builders on packed dict views (one agent index per view).
 __global__ __launch_bounds__(256) void k_views_alt(DevParams p, const int32_t* __restrict__ views,
                                                    const int64_t* __restrict__ offs, int n,
@@ -2062,6 +2148,22 @@ hipError_t launch_alt_obs(const DevParams& p, int env_begin, int n, float* idq, 
     else
         hipLaunchKernelGGL(k_alt_obs<false>, dim3(blocks_for(n, wpb)), dim3(256), lds * wpb, s, p, env_begin, n, idq,
                            qst, oh, ow, wpb, (int)lds);
+    return hipGetLastError();
+}
+
+size_t alt_pre_size(int E, int A) { return alt_pre_bytes(E, A); }
+
+hipError_t launch_alt_transition(const DevParams& p, const uint8_t* acts, int fmt, int ops_are_ints,
+                                 const uint8_t* mask, void* pre, double* r_idq, float* idq, float* qst, int oh, int ow,
+                                 int wpb, size_t lds, hipStream_t s) {
+    AltPre* pr = (AltPre*)pre;
+    int32_t* pt = (int32_t*)((char*)pre + alt_pre_t_off(p.E, p.A));
+    if (p.stale)
+        hipLaunchKernelGGL(k_alt_transition<true>, dim3(blocks_for(p.E, wpb)), dim3(256), lds * wpb, s, p, acts, fmt,
+                           ops_are_ints, mask, pr, pt, r_idq, idq, qst, oh, ow, wpb, (int)lds);
+    else
+        hipLaunchKernelGGL(k_alt_transition<false>, dim3(blocks_for(p.E, wpb)), dim3(256), lds * wpb, s, p, acts, fmt,
+                           ops_are_ints, mask, pr, pt, r_idq, idq, qst, oh, ow, wpb, (int)lds);
     return hipGetLastError();
 }
 

@@ -133,6 +133,11 @@ hipError_t launch_views_idq_reward(const int32_t* prev, const int64_t* prev_offs
                                    const int64_t* cur_offs, const uint8_t* ops, const int64_t* op_offs,
                                    int ops_are_ints, int n, double* out, int wpb, size_t lds, int NSmax,
                                    hipStream_t s);
+// k_alt_transition over all p.E envs; pre: the caller's record of alt_pre_size(E, A) bytes
+hipError_t launch_alt_transition(const DevParams& p, const uint8_t* acts, int fmt, int ops_are_ints,
+                                 const uint8_t* mask, void* pre, double* r_idq, float* idq, float* qst, int oh, int ow,
+                                 int wpb, size_t lds, hipStream_t s);
+size_t alt_pre_size(int E, int A);
 size_t alt_obs_lds(int P, int HW);
 size_t views_alt_lds(int NSmax, int HW);
 

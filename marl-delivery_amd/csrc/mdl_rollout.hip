@@ -9,6 +9,8 @@
 //             (the same Philox keying; include/mdl_engine.h states the draw)
 //   k_gae     the GAE recursion of MAPPO/trainer.py:266-276, same float32
 //             operation order as the reference's torch expressions
+//   k_replay_rank / k_replay_copy  one step's ReplayBuffer.add calls   IDQ/trainer.py:304-311
+//             (a compacting append to the transition ring, cursor on the device)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -170,6 +172,94 @@ __global__ void k_counter_add(uint64_t* __restrict__ c, uint64_t v) {
     if (threadIdx.x == 0) *c += v;
 }
 
+// ---- IDQ's per-transition replay ring (ReplayBuffer.add, IDQ/networks.py:63-79), one step's
+// buffer.add calls (IDQ/trainer.py:304-311): env-then-agent order over the envs `filled` marks.
+//
+// k_replay_rank, ONE workgroup: rank[e] = number of filled envs before e (chunks of 256 envs: a
+// ballot per wave, the waves' counts through LDS, a running carry), then thread 0 stores the
+// filled count and the ring position this step starts at behind the ranks and advances the cursor.
+__global__ __launch_bounds__(256) void k_replay_rank(const uint8_t* __restrict__ filled, int E, int A,
+                                                     int64_t capacity, int64_t* __restrict__ cursor,
+                                                     int32_t* __restrict__ rank) {
+    __shared__ int wsum[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int carry = 0;
+    for (int c0 = 0; c0 < E; c0 += 256) {
+        const int e = c0 + tid;
+        const bool f = e < E && filled[e] != 0;
+        const uint64_t b = __ballot(f);
+        if (lane == 0) wsum[wave] = __popcll(b);
+        __syncthreads();
+        int before = carry, all = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int s = wsum[k];
+            before += k < wave ? s : 0;
+            all += s;
+        }
+        if (e < E) rank[e] = before + __popcll(b & ((1ull << lane) - 1ull));
+        carry += all;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const int64_t ptr = cursor[0], size = cursor[1];
+        const int64_t rows = (int64_t)carry * A;
+        rank[E] = carry;
+        rank[E + 1] = (int32_t)(uint32_t)ptr;
+        rank[E + 2] = (int32_t)(ptr >> 32);
+        cursor[0] = (ptr + rows) % capacity;
+        cursor[1] = size + rows < capacity ? size + rows : capacity;
+    }
+}
+
+// k_replay_copy, one wave per env: row i = rank*A + a of the step goes to slot (base + i) %
+// capacity; of a step with more rows than the ring only the last `capacity` are written (what
+// the sequential adds leave), so no two waves write one slot.  VEC: rows as 16-byte vectors.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_replay_copy(const uint8_t* __restrict__ filled, int E, int A,
+                                                     int64_t row_floats, const float* __restrict__ obs,
+                                                     const float* __restrict__ next_obs,
+                                                     const uint8_t* __restrict__ actions,
+                                                     const double* __restrict__ reward,
+                                                     const uint8_t* __restrict__ done, int64_t capacity,
+                                                     const int32_t* __restrict__ rank, float* __restrict__ ring_obs,
+                                                     float* __restrict__ ring_next, int64_t* __restrict__ ring_action,
+                                                     float* __restrict__ ring_reward, uint8_t* __restrict__ ring_done) {
+    const int lane = threadIdx.x & 63;
+    const int e = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (e >= E || filled[e] == 0) return;
+    const int64_t rows = (int64_t)rank[E] * A;
+    const int64_t base = (int64_t)((uint64_t)(uint32_t)rank[E + 1] | ((uint64_t)(uint32_t)rank[E + 2] << 32));
+    const int64_t first = rows > capacity ? rows - capacity : 0;
+    const uint8_t dn = done[e];
+    for (int a = 0; a < A; a++) {
+        const int64_t i = (int64_t)rank[e] * A + a;
+        if (i < first) continue;
+        const int64_t slot = (base + i) % capacity;
+        const int64_t src = ((int64_t)e * A + a) * row_floats, dst = slot * row_floats;
+        if (VEC) {
+            const float4* so = reinterpret_cast<const float4*>(obs + src);
+            const float4* sn = reinterpret_cast<const float4*>(next_obs + src);
+            float4* po = reinterpret_cast<float4*>(ring_obs + dst);
+            float4* pn = reinterpret_cast<float4*>(ring_next + dst);
+            for (int64_t k = lane; k < row_floats / 4; k += 64) {
+                po[k] = so[k];
+                pn[k] = sn[k];
+            }
+        } else {
+            for (int64_t k = lane; k < row_floats; k += 64) {
+                ring_obs[dst + k] = obs[src + k];
+                ring_next[dst + k] = next_obs[src + k];
+            }
+        }
+        if (lane == 0) {
+            ring_action[slot] = (int64_t)actions[(int64_t)e * A + a];
+            ring_reward[slot] = (float)reward[(int64_t)e * A + a];   // fp64 -> float32, rounded once
+            ring_done[slot] = dn;
+        }
+    }
+}
+
 }  // namespace mdl
 
 namespace {
@@ -253,6 +343,34 @@ int mdl_counter_add(uint64_t* counter, uint64_t value, void* stream) {
     hipLaunchKernelGGL(mdl::k_counter_add, dim3(1), dim3(64), 0, (hipStream_t)stream, counter, value);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : rfail("mdl_counter_add: launch failed", e);
+}
+
+int mdl_replay_append(const uint8_t* filled, int32_t E, int32_t A, int64_t row_floats, const float* obs,
+                      const float* next_obs, const uint8_t* actions, const double* reward, const uint8_t* done,
+                      int64_t capacity, int64_t* cursor, float* ring_obs, float* ring_next_obs, int64_t* ring_action,
+                      float* ring_reward, uint8_t* ring_done, int32_t* rank_scratch, void* stream) {
+    if (!filled || !obs || !next_obs || !actions || !reward || !done || !cursor || !ring_obs || !ring_next_obs ||
+        !ring_action || !ring_reward || !ring_done || !rank_scratch)
+        return rfail("mdl_replay_append: null argument");
+    if (E < 0 || E > MDL_REPLAY_MAX_ENVS || A < 1 || A > MDL_MAX_ROBOTS || row_floats < 1 || capacity < 1)
+        return rfail("mdl_replay_append: bad sizes (E <= MDL_REPLAY_MAX_ENVS)");
+    if (E == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(mdl::k_replay_rank, dim3(1), dim3(256), 0, s, filled, (int)E, (int)A, capacity, cursor,
+                       rank_scratch);
+    const bool vec = row_floats % 4 == 0 &&
+                     (((uintptr_t)obs | (uintptr_t)next_obs | (uintptr_t)ring_obs | (uintptr_t)ring_next_obs) & 15) == 0;
+    const dim3 g((unsigned)((E + 3) / 4)), b(256);
+    if (vec)
+        hipLaunchKernelGGL(mdl::k_replay_copy<true>, g, b, 0, s, filled, (int)E, (int)A, row_floats, obs, next_obs,
+                           actions, reward, done, capacity, rank_scratch, ring_obs, ring_next_obs, ring_action,
+                           ring_reward, ring_done);
+    else
+        hipLaunchKernelGGL(mdl::k_replay_copy<false>, g, b, 0, s, filled, (int)E, (int)A, row_floats, obs, next_obs,
+                           actions, reward, done, capacity, rank_scratch, ring_obs, ring_next_obs, ring_action,
+                           ring_reward, ring_done);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : rfail("mdl_replay_append: launch failed", e);
 }
 
 int mdl_gae(const float* rewards, const float* values, const float* next_value, const uint8_t* dones, int32_t T,

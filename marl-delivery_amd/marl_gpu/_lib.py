@@ -30,6 +30,7 @@ MDL_ACTION_TRAINER_INT = 0
 MDL_ACTION_CODES = 1
 MDL_MAX_ROBOTS = 64
 MDL_MAX_PACKAGES = 1024
+MDL_REPLAY_MAX_ENVS = 65536
 MDL_OBS_BUILDER_AUTO = 0
 MDL_OBS_BUILDER_GENERIC = 1
 MDL_STEP_LAYOUT_AUTO = 0
@@ -83,6 +84,8 @@ SIGNATURES = {
     "mdl_step_floor": (C.c_int, [_vp, _i32, _vp]),
     "mdl_build_obs": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "mdl_build_obs_alt": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp]),
+    "mdl_alt_pre_bytes": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
+    "mdl_alt_transition": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "mdl_views_alt_features": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp]),
     "mdl_views_idq_reward": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),
     "mdl_greedy_init": (C.c_int, [_vp, _vp, _i32, _vp]),
@@ -101,6 +104,8 @@ SIGNATURES = {
     "mdl_select_actions_eps": (C.c_int, [_vp, _vp, C.c_int64, _i32, C.c_float, C.c_uint64, C.c_uint64, _vp, _vp]),
     "mdl_select_actions_eps_dev": (C.c_int, [_vp, _vp, C.c_int64, _i32, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp]),
     "mdl_counter_add": (C.c_int, [_vp, C.c_uint64, _vp]),
+    "mdl_replay_append": (C.c_int, [_vp, _i32, _i32, C.c_int64, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp,
+                                    _vp, _vp, _vp, _vp]),
     "mdl_gae": (C.c_int, [_vp, _vp, _vp, _vp, _i32, C.c_int64, C.c_float, C.c_float, _vp, _vp, _vp]),
     "mdl_read_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mdl_views_features": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32,

@@ -503,6 +503,64 @@ class BatchedEnv:
                                       oh, ow, self._stream()), "mdl_build_obs_alt")
         return out
 
+    def alt_pre_buffer(self) -> torch.Tensor:
+        """The pre-record of ``alt_transition`` (uint8, ``mdl_alt_pre_bytes`` long): what
+        reward_shaping reads of the state and the tracker from before a step."""
+        nb = C.c_int64(0)
+        check(lib().mdl_alt_pre_bytes(self._h, C.byref(nb)), "mdl_alt_pre_bytes")
+        return torch.zeros(nb.value, dtype=torch.uint8, device=self.device)
+
+    def alt_transition(self, actions, pre: torch.Tensor, row_mask: torch.Tensor | None = None,
+                       ops_are_ints: bool = False, out: dict | None = None, state_shape=None, which=("idq_obs",),
+                       action_format: str = "int", r_out: torch.Tensor | None = None):
+        """The IDQ trainer's work after a step (IDQ/trainer.py:286-311) for all E envs: per-agent
+        reward_shaping (IDQ/networks.py:228-349) of the transition the engine just made with
+        ``actions`` (uint8 [E, A]), from ``pre`` (``alt_pre_buffer()``: the record the previous
+        call left of the state and tracker before the step), then the new record and
+        ``build_obs_alt``'s observations of the new state.  An env whose byte of ``row_mask``
+        (uint8 [E], e.g. ``step_episode``'s ``filled``) is 0 gets reward 0 and keeps its rows of
+        the observations and of ``pre``.  ``actions=None`` is the begin form (after a reset): no
+        reward.  ops_are_ints=False reproduces the trainer, which hands reward_shaping string
+        ops.  Returns (r_idq f64 [E, A] or None, obs dict)."""
+        n = self.E
+        if self._shape_run_end[0] < n:
+            raise ValueError("alt_transition: the envs mix map shapes (build one engine per map shape)")
+        H, W = self.grids[int(self.env_map[0])].shape
+        oh, ow = (H, W) if state_shape is None else (int(state_shape[1]), int(state_shape[2]))
+        if not isinstance(pre, torch.Tensor) or pre.dtype != torch.uint8 or not pre.is_cuda \
+                or pre.get_device() != self.device.index or not pre.is_contiguous():
+            raise TypeError(f"pre must be a contiguous uint8 tensor on {self.device} (alt_pre_buffer())")
+        if pre.numel() < n * self.A * 16 + n * 4:
+            raise ValueError(f"pre holds {pre.numel()} bytes, needs {n * self.A * 16 + n * 4}")
+        if row_mask is not None:
+            self._check_mask(row_mask, "row_mask")
+        f = dict(dtype=torch.float32, device=self.device)
+        if out is None:
+            out = {}
+            if "idq_obs" in which:
+                out["idq_obs"] = torch.empty((n, self.A, 6, H, W), **f)
+            if "qmix_state" in which:
+                out["qmix_state"] = torch.empty((n, 7, oh, ow), **f)
+        p = {k: (out.get(k) if k in which else None) for k in ("idq_obs", "qmix_state")}
+        if p["idq_obs"] is not None:
+            self._check_obs_out(p["idq_obs"], "idq_obs", (n, self.A, 6, H, W))
+        if p["qmix_state"] is not None:
+            self._check_obs_out(p["qmix_state"], "qmix_state", (n, 7, oh, ow))
+        if actions is not None:
+            actions = self._step_args(actions, n)
+            if r_out is None:
+                r_out = torch.empty((n, self.A), dtype=torch.float64, device=self.device)
+            elif r_out.dtype != torch.float64 or not r_out.is_cuda or r_out.get_device() != self.device.index \
+                    or not r_out.is_contiguous() or r_out.numel() < n * self.A:
+                raise TypeError(f"r_out must be a contiguous float64 tensor of {n * self.A} entries on {self.device}")
+        else:
+            r_out = None
+        check(lib().mdl_alt_transition(self._h, ptr(actions), ACTION_FORMATS[action_format], 1 if ops_are_ints else 0,
+                                       ptr(row_mask), pre.data_ptr(), ptr(r_out), ptr(p["idq_obs"]),
+                                       ptr(p["qmix_state"]), oh, ow, self._stream()), "mdl_alt_transition")
+        self._keep = (None, actions)
+        return r_out, {k: v for k, v in p.items() if v is not None}
+
     # ---- greedy baseline (SURVEY.md §8(f)3): greedyagent.py batched on the device ----
     def greedy_init(self, env_ids=None):
         """``GreedyAgents()`` + ``init_agents(state)`` for the listed envs (right after their reset)."""

@@ -12,6 +12,8 @@
   --config greedy   batched greedy baseline (§8(f)3)
   --qmix            QMIX episode collection: the masked step against the full step, and one collector
                     step against the host-driven subset loop
+  --idq             IDQ transition collection: alt_transition against build_obs_alt, and one collector
+                    step against the host-driven loop it replaces
 
 Prints one JSON line per config with per-kernel HIP-event times and the
 algorithmic-bytes roofline of SURVEY.md §8(d).
@@ -387,6 +389,169 @@ def run_qmix(steps):
         ref.close()
 
 
+def _pack_idq_views(s0, s1, idx, A, P):
+    """Host side of mdl_views_idq_reward for the envs ``idx``: the previous states with their
+    trackers as view records of fixed width, the current robot records, the offsets (numpy)."""
+    n = idx.size
+    vw, cw = 4 + 3 * A + 8 * P, 2 + 3 * A
+    trk, data = s0["tracker"][idx], s0["tracker_data"][idx]
+    pres = trk[:, :, 0] != 0
+    order = np.argsort(~pres, axis=1, kind="stable")                 # present slots first
+    rows = np.zeros((n, P, 8), np.int32)
+    rows[:, :, 0] = order + 1
+    rows[:, :, 1] = np.where(np.take_along_axis(trk[:, :, 1], order, 1) != 0, 2, 1)
+    rows[:, :, 2:] = np.take_along_axis(data, order[:, :, None], 1)
+    views = np.zeros((n, vw), np.int32)
+    views[:, 0] = s0["t"][idx]
+    views[:, 1] = A
+    views[:, 2] = pres.sum(1)
+    views[:, 4:4 + 3 * A] = s0["robots"][idx].reshape(n, 3 * A)
+    views[:, 4 + 3 * A:] = rows.reshape(n, 8 * P)
+    cur = np.zeros((n, cw), np.int32)
+    cur[:, 0] = s1["t"][idx]
+    cur[:, 1] = A
+    cur[:, 2:] = s1["robots"][idx].reshape(n, 3 * A)
+    ar = np.arange(n, dtype=np.int64)
+    return views, cur, ar * vw, ar * cw, ar * A
+
+
+def run_idq(steps):
+    """IDQ transition collection ("IDQ transition collection"); map1, A=5, P=20, fresh
+    tracker, 4 and 4,096 envs, every env running.
+
+    1. ``alt_transition`` alone against ``build_obs_alt`` alone on the same envs and state
+       (idq_obs only), hipGraph-replayed, five repeats each, interleaved: the cost of the row mask,
+       the reward and the pre-record.
+    2. One ``IdqCollector`` step (selection, ``step_episode``, ``alt_transition``, the replay
+       append; the agent's forward replaced by preset Q-values), eager and graph-replayed, against
+       the host-driven loop the engine allowed before, five interleaved repeats: done mask read
+       back, subset ``step``, ``read_state`` before and after the step, views packed on the host
+       and uploaded, ``mdl_views_idq_reward``, ``build_obs_alt``, torch indexed ring writes.
+    """
+    import marl_gpu
+    from marl_gpu._lib import check, lib, ptr, stream_handle
+    from marl_gpu.idq_rollout import IdqCollector, TransitionReplay
+    from marl_gpu.maps import grid_array, load_map, map_path
+    g1 = grid_array(load_map(map_path("map1.txt")))
+    H, W = g1.shape
+    A, P, T, G = 5, 20, 500, 50
+    dev = torch.device("cuda", 0)
+    gen = torch.Generator(device=dev).manual_seed(0)
+    reps = max(2, steps // G)
+    for E in (4, 4096):
+        env = marl_gpu.BatchedEnv(g1, E, A, P, T, seed=42, tracker="fresh")
+        env.reset()
+        acts = torch.randint(0, 15, (E, A), generator=gen, device=dev, dtype=torch.int32).to(torch.uint8)
+        for _ in range(30):
+            env.step(acts, auto_reset=False)
+        obs = {"idq_obs": torch.zeros((E, A, 6, H, W), dtype=torch.float32, device=dev)}
+        pre = env.alt_pre_buffer()
+        ones = torch.ones(E, dtype=torch.uint8, device=dev)
+        r = torch.zeros((E, A), dtype=torch.float64, device=dev)
+        env.alt_transition(None, pre, out=obs)
+
+        def many(fn):
+            def f():
+                for _ in range(G):
+                    fn()
+            return f
+
+        gb = _graph_of(many(lambda: env.build_obs_alt(out=obs, which=("idq_obs",))))
+        gt = _graph_of(many(lambda: env.alt_transition(acts, pre, ops_are_ints=True, out=obs, r_out=r)))
+        gm = _graph_of(many(lambda: env.alt_transition(acts, pre, row_mask=ones, ops_are_ints=True, out=obs, r_out=r)))
+        tb, tt, tm = [], [], []
+        for _ in range(5):
+            tb.append(_replay_us(gb, reps, G))
+            tt.append(_replay_us(gt, reps, G))
+            tm.append(_replay_us(gm, reps, G))
+        print(json.dumps({"config": "idq_alt_transition", "envs": E, "agents": A, "packages": P, "graph_calls": G,
+                          "replays": reps, "build_obs_alt_us": tb, "alt_transition_us": tt,
+                          "alt_transition_masked_us": tm, "build_obs_alt_spread_us": max(tb) - min(tb),
+                          "median_gap_us": float(np.median(tt) - np.median(tb)),
+                          "median_gap_masked_us": float(np.median(tm) - np.median(tb)),
+                          "note": "us per call, idq_obs only, same envs and state; masked = row_mask all ones"}),
+              flush=True)
+        env.close()
+
+    for E in (4, 4096):
+        cap = 1 << 16
+        env = marl_gpu.BatchedEnv(g1, E, A, P, T, seed=42, tracker="fresh")
+        ref = marl_gpu.BatchedEnv(g1, E, A, P, T, seed=42, tracker="fresh")
+        q = torch.randn(E * A, 15, generator=gen, device=dev)
+        agent = lambda o: q   # noqa: E731  (stand-in for the network's forward)
+        col = IdqCollector(env, TransitionReplay(cap, (6, H, W), device=dev), seed=1, ops_are_ints=True)
+
+        # the host-driven loop
+        ring = TransitionReplay(cap, (6, H, W), device=dev)   # only its tensors: written by torch indexing
+        o2 = [torch.zeros((E, A, 6, H, W), dtype=torch.float32, device=dev) for _ in range(2)]
+        st = {"done": torch.zeros(E, dtype=torch.uint8, device=dev), "mask": np.ones(E, bool), "ptr": 0, "cur": 0}
+        a_all = q.view(E, A, 15)[:, :, 0].gt(0).to(torch.uint8)   # stand-in actions
+
+        def host_step(k):
+            st["mask"] &= ~st["done"].cpu().numpy().astype(bool)                      # done mask read back
+            idx = np.nonzero(st["mask"])[0]
+            n = idx.size
+            ids = torch.from_numpy(idx.astype(np.int32)).to(dev)
+            il = ids.long()
+            a = a_all[il].contiguous()
+            s0 = {k2: v.cpu().numpy() for k2, v in ref.read_state().items()}           # state before the step
+            _, _, dn = ref.step(a, env_ids=ids, auto_reset=False)
+            st["done"].zero_()
+            st["done"][il] = dn
+            s1 = {k2: v.cpu().numpy() for k2, v in ref.read_state().items()}           # and after it
+            views, cur, vo, co, oo = _pack_idq_views(s0, s1, idx, A, P)
+            dv, dc = torch.from_numpy(views).to(dev), torch.from_numpy(cur).to(dev)
+            dvo, dco, doo = (torch.from_numpy(x).to(dev) for x in (vo, co, oo))
+            rw = torch.empty(n * A, dtype=torch.float64, device=dev)
+            check(lib().mdl_views_idq_reward(ref._h, ptr(dv), ptr(dvo), P, ptr(dc), ptr(dco), ptr(a), ptr(doo), 1, n,
+                                             ptr(rw), stream_handle(dev)), "mdl_views_idq_reward")
+            c = st["cur"]
+            ref.build_obs_alt(out={"idq_obs": o2[1 - c]}, which=("idq_obs",))
+            slots = (torch.arange(n * A, device=dev) + st["ptr"]) % cap                # the ring writes
+            ring.observations[slots] = o2[c][il].reshape(n * A, 6, H, W)
+            ring.next_observations[slots] = o2[1 - c][il].reshape(n * A, 6, H, W)
+            ring.actions[slots] = a.reshape(-1).long()
+            ring.rewards[slots] = rw.float()
+            ring.dones[slots] = dn.repeat_interleave(A)
+            st["ptr"] = (st["ptr"] + n * A) % cap
+            st["cur"] = 1 - c
+
+        def host_begin():
+            ref.reset()
+            st["done"].zero_()
+            st["mask"][:] = True
+            st["cur"] = 0
+            ref.build_obs_alt(out={"idq_obs": o2[0]}, which=("idq_obs",))
+
+        host_begin()
+        for k in range(5):   # torch's indexing kernels and the copy paths, once
+            host_step(k)
+        col.begin()
+        for k in range(5):
+            col.step(agent, 0.2)
+        col.collect(agent, 0.2, max_steps=G, graph=True)   # eager run + capture
+        te, tg, th = [], [], []
+        for _ in range(5):
+            col.begin()
+            te.append(timed(lambda k: col.step(agent, 0.2), G))
+            tg.append(timed(lambda k: col.collect(agent, 0.2, max_steps=G, graph=True), reps) / G)
+            host_begin()
+            th.append(timed(host_step, G))
+        assert col._graph is not None and bool(col.active.all()), "an env ended inside the measured collect"
+        print(json.dumps({"config": "idq_collector_step", "envs": E, "agents": A, "packages": P, "steps": G,
+                          "collector_step_graph_us": tg, "collector_step_eager_us": te, "host_loop_step_us": th,
+                          "graph_spread_us": max(tg) - min(tg), "eager_spread_us": max(te) - min(te),
+                          "host_spread_us": max(th) - min(th),
+                          "launches": {"collector": "5 kernels (k_select_eps, k_step_episode, k_alt_transition, "
+                                                    "k_replay_rank, k_replay_copy), no copy, no sync; the graph figure "
+                                                    "holds 1/50 of the collect's reset, begin and return read",
+                                       "host_loop": "k_step (subset), 2 k_export, k_views_idq_reward, k_alt_obs, the torch "
+                                                    "gather/scatter kernels, 13 D2H + 6 H2D copies per step"}}),
+              flush=True)
+        env.close()
+        ref.close()
+
+
 def run_config1(seconds=5.0):
     """BASELINE.json configs[0]: map1, 5 agents, ONE env, a random agent driving the dict
     API (randomagent.py: np.random.choice over moves and ops per robot) -- plumbing, not a
@@ -423,10 +588,14 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--qmix", action="store_true", help="the QMIX episode-collection measurements only")
+    ap.add_argument("--idq", action="store_true", help="the IDQ transition-collection measurements only")
     a = ap.parse_args()
     torch.cuda.set_device(0)
     if a.qmix:
         run_qmix(a.steps)
+        return
+    if a.idq:
+        run_idq(a.steps)
         return
     for c in a.config.split(","):
         if c == "1":
