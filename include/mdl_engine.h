@@ -206,6 +206,26 @@ int mdl_alt_transition(MdlEngine* eng, const uint8_t* actions, int32_t action_fo
                        const uint8_t* row_mask, void* pre, double* r_idq, float* idq_obs, float* qmix_state,
                        int32_t out_h, int32_t out_w, void* stream);
 
+/* The lazy reset that opens a time step of the map-QMIX cycle (QMixTrainer.collect_and_train_cycle,
+ * qmix/trainer.py:329-346), for all E envs (one map shape), row e = env e, one launch.  All pointers
+ * DEVICE.  done: the caller's uint8 [E], read and updated here.
+ *   done[e] != 0, in this order: completed[e] = 1; completed_return[e] = the env's total_reward (the
+ *     trainer's env_episode_rewards: the same fp64 sum in the same order); completed_steps[e] = t; the
+ *     env's tracker is emptied and Environment.reset() runs (qmix/trainer.py:334-336) -- the engine
+ *     state afterwards, the env's MT19937 state included, is what mdl_tracker_clear(ids) followed by
+ *     mdl_reset(ids) leaves, in both tracker modes (stale: the reset's own tracker update on the empty
+ *     tracker); done[e] = 0; rows e of idq_obs (f32 [E][A][6][H][W]) and qmix_state (f32
+ *     [E][7][out_h][out_w]) receive what mdl_build_obs_alt writes for the new state.
+ *   done[e] == 0: completed[e] = 0, completed_return[e] = 0.0, completed_steps[e] = 0; nothing else of
+ *     env e is read or written, its rows of the two tensors stay as they are.
+ * The launch resets what the mask marks; it does not look at t.  Any of completed, completed_return,
+ * completed_steps, idq_obs and qmix_state may be NULL.  The buffers must not overlap one another: done
+ * and completed in particular are two buffers.  The engine gains no state (checkpoints are unaffected).
+ * Captures into a hipGraph. */
+int mdl_cycle_begin(MdlEngine* eng, uint8_t* done, uint8_t* completed, double* completed_return,
+                    int32_t* completed_steps, float* idq_obs, float* qmix_state, int32_t out_h, int32_t out_w,
+                    void* stream);
+
 /* ---- greedy baseline: greedyagent.py batched on the device ----
  * mdl_greedy_init = GreedyAgents() + init_agents(state) for the listed envs (call it right
  * after their reset, as evaluation.py:29-35 does); the first call also builds run_bfs's
@@ -339,6 +359,15 @@ int mdl_select_actions_eps(const float* q, const uint8_t* avail, int64_t n_rows,
 int mdl_select_actions_eps_dev(const float* q, const uint8_t* avail, int64_t n_rows, int32_t n_actions,
                                const float* epsilon_dev, uint64_t seed, const uint64_t* offset_dev,
                                uint64_t offset_add, uint8_t* actions, void* stream);
+/* The same selections (bit-identical actions), which also report the rows that explored: explored uint8
+ * [n_rows] = 1 where the row explored (float(x0 >> 8) * 2^-24 < epsilon and it had an available action),
+ * else 0.  qmix/trainer.py:251-260 keeps an exploring agent's hidden state. */
+int mdl_select_actions_eps_mark(const float* q, const uint8_t* avail, int64_t n_rows, int32_t n_actions,
+                                float epsilon, uint64_t seed, uint64_t offset, uint8_t* actions, uint8_t* explored,
+                                void* stream);
+int mdl_select_actions_eps_mark_dev(const float* q, const uint8_t* avail, int64_t n_rows, int32_t n_actions,
+                                    const float* epsilon_dev, uint64_t seed, const uint64_t* offset_dev,
+                                    uint64_t offset_add, uint8_t* actions, uint8_t* explored, void* stream);
 
 /* *counter += value on the device (stream-ordered; advances offset_dev inside a graph). */
 int mdl_counter_add(uint64_t* counter, uint64_t value, void* stream);
@@ -362,6 +391,25 @@ int mdl_replay_append(const uint8_t* filled, int32_t E, int32_t A, int64_t row_f
                       const float* next_obs, const uint8_t* actions, const double* reward, const uint8_t* done,
                       int64_t capacity, int64_t* cursor, float* ring_obs, float* ring_next_obs, int64_t* ring_action,
                       float* ring_reward, uint8_t* ring_done, int32_t* rank_scratch, void* stream);
+
+/* One step's appends to the qmix/ trainer's joint replay buffer (ReplayBuffer.add, qmix/networks.py:155-198,
+ * called for every env of the step: qmix/trainer.py:380-389), needing no engine.  In env order, ring slot
+ * (ptr + e) % capacity receives state[e] and next_state[e] (f32, state_floats each), obs[e] and
+ * next_obs[e] (f32, A * obs_floats each), actions[e][0..A) (uint8 -> int64), reward[e] (f64 -> f32,
+ * rounded once) and done[e] (uint8); then ptr = (ptr + E) % capacity and size = min(size + E, capacity).
+ * All pointers DEVICE; cursor int64 [2] = (ptr, size).  The ring: ring_state, ring_next_state f32
+ * [capacity][state_floats]; ring_obs, ring_next_obs f32 [capacity][A * obs_floats]; ring_action int64
+ * [capacity][A]; ring_reward f32 and ring_done uint8 [capacity].  Of a step with E > capacity only the
+ * last `capacity` rows are written, each once.  Two launches, so that the cursor is never read and
+ * advanced in one grid: the copy, one wave per env, reads it (16-byte vectors where state_floats and
+ * A * obs_floats are multiples of 4 and the eight row pointers are 16-byte aligned); a one-thread
+ * launch then advances it.  Both capture into a hipGraph.  The step's rows must not overlap the ring
+ * (state and next_state, or obs and next_obs, may be one buffer: they are only read). */
+int mdl_replay_append_joint(int32_t E, int32_t A, int64_t state_floats, int64_t obs_floats, const float* state,
+                            const float* next_state, const float* obs, const float* next_obs, const uint8_t* actions,
+                            const double* reward, const uint8_t* done, int64_t capacity, int64_t* cursor,
+                            float* ring_state, float* ring_next_state, float* ring_obs, float* ring_next_obs,
+                            int64_t* ring_action, float* ring_reward, uint8_t* ring_done, void* stream);
 
 /* Generalised advantage estimation exactly as MAPPO/trainer.py:266-276 computes it in float32
  * (same operation order): rewards, values, dones [T][n] (dones uint8), next_value [n];

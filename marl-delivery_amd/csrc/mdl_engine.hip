@@ -1259,6 +1259,26 @@ int mdl_alt_transition(MdlEngine* eng, const uint8_t* actions, int32_t action_fo
     return 0;
 }
 
+int mdl_cycle_begin(MdlEngine* eng, uint8_t* done, uint8_t* completed, double* completed_return,
+                    int32_t* completed_steps, float* idq_obs, float* qmix_state, int32_t out_h, int32_t out_w,
+                    void* stream) {
+    if (!eng || !done) return fail("mdl_cycle_begin: null argument");
+    if (!eng->seeded) return fail("mdl_cycle_begin: engine not seeded (call mdl_seed first)");
+    if (qmix_state && (out_h < 1 || out_w < 1 || out_h > 4096 || out_w > 4096))
+        return fail("mdl_cycle_begin: bad state tensor shape (%d, %d)", out_h, out_w);
+    const int E = eng->p.E;
+    if (eng->shape_run_end[0] < E)
+        return fail("mdl_cycle_begin: envs [%d, %d) mix map shapes (same-shape run ends at %d)", 0, E,
+                    eng->shape_run_end[0]);
+    const size_t lds = mdl::cycle_begin_lds(eng->p.P, eng->maxHW);
+    const int wpb = waves_per_block(lds);
+    if (wpb < 1) return fail("mdl_cycle_begin: needs %zu bytes of LDS per env", lds);
+    DeviceGuard dg(eng->device);
+    HIPCHK(mdl::launch_cycle_begin(eng->p, done, completed, completed_return, completed_steps, idq_obs, qmix_state,
+                                   out_h, out_w, wpb, lds, (hipStream_t)stream));
+    return 0;
+}
+
 int mdl_views_alt_features(MdlEngine* eng, const int32_t* views, const int64_t* offsets, int32_t n_views,
                            int32_t max_slots, const int32_t* agent_idx, float* idq_obs, float* qmix_state,
                            int32_t out_h, int32_t out_w, void* stream) {

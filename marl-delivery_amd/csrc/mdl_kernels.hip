@@ -1722,6 +1722,113 @@ __global__ __launch_bounds__(256) void k_alt_transition(DevParams p, const uint8
     }
 }
 
+// mdl_cycle_begin: the lazy reset that opens a time step of the map-QMIX cycle
+// (QMixTrainer.collect_and_train_cycle, qmix/trainer.py:329-346) for the envs `done` marks: the
+// finished episode's return and length, tracker.clear() + Environment.reset() (== k_tracker_clear
+// then k_reset), done[e] = 0, and k_alt_obs's observations of the reset state into row e.
+// An unmarked wave writes its three zeros and leaves before any state load.
+//
+// LDS per wave: the reset scratch, then the builder's per-cell scratch (AltLds).  The builder's
+// tracker slots (k_alt_obs's ObsLdsPre) are not staged again: they overlap the reset scratch.  After
+// do_reset L.pk is the new package table and L.pst its status bytes, which is what a fresh tracker
+// is; a stale tracker, emptied and then updated with the reset state, has no survivor, so its
+// entry data is L.pk as well, its flag bytes go back into L.pst (each lane its own slots) and the
+// order keys into L.scratch, which the reset's sort has finished reading.  The robot cell stays in
+// the lane; t = 0 and nothing is carried.  Nothing written to HBM here is read back.
+template <bool STALE, int NCH>
+__global__ __launch_bounds__(256) void k_cycle_begin(DevParams p, uint8_t* __restrict__ done,
+                                                     uint8_t* __restrict__ completed, double* __restrict__ c_return,
+                                                     int32_t* __restrict__ c_steps, float* __restrict__ idq,
+                                                     float* __restrict__ qst, int oh, int ow, int wpb,
+                                                     int lds_stride) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int wave = wave_id();
+    const int lane = lane_id();
+    const int e = blockIdx.x * wpb + wave;
+    if (wave >= wpb || e >= p.E) return;
+    if (!done[e]) {
+        if (lane == 0) {
+            if (completed) completed[e] = 0;
+            if (c_return) c_return[e] = 0.0;
+            if (c_steps) c_steps[e] = 0;
+        }
+        return;
+    }
+    const int A = p.A, P = p.P;
+    unsigned char* base = smem + (size_t)wave * lds_stride;
+    ResetLds L = reset_carve(base, P);
+    const MapDesc md = p.maps[p.env_map ? p.env_map[e] : 0];
+    const int H = md.H, W = md.W;
+    AltLds AL = alt_carve(base + reset_lds_bytes(P), H * W);
+    if (lane == 0) {
+        const EnvScalars s = p.es[e];
+        if (completed) completed[e] = 1;
+        if (c_return) c_return[e] = s.total;
+        if (c_steps) c_steps[e] = s.t;
+    }
+    const int cell = do_reset(p, e, md, L, false);
+    // the emptied tracker has no entry to survive the reset (survivors_at_reset would leave the
+    // status bits alone): the reset's own update inserts the t = 0 packages, as k_reset does
+    uint32_t ps[NCH];
+    uint64_t pk[NCH], td[NCH];
+    bool dirty[NCH];
+#pragma unroll
+    for (int c = 0; c < NCH; c++) {
+        const int j = c * WAVE + lane;
+        pk[c] = j < P ? L.pk[j] : 0;
+        ps[c] = j < P ? L.pst[j] : 0u;
+        td[c] = pk[c];
+        dirty[c] = false;
+    }
+    if (STALE) tracker_update_regs<NCH>(ps, td, dirty, pk, P, A, 0, 0);
+    if (lane < A)
+        p.rob[(size_t)e * A + lane] = rob_pack(cell, 0, p.movevalid[md.grid_off + cell_r(cell) * md.W + cell_c(cell)]);
+#pragma unroll
+    for (int c = 0; c < NCH; c++) {
+        const int j = c * WAVE + lane;
+        if (j < P) {
+            const size_t g = (size_t)e * P + j;
+            p.pkg[g] = pk[c];
+            p.pstate[g] = (uint16_t)ps[c];
+            if (dirty[c]) p.trk[g] = td[c];
+            if (STALE) {
+                L.pst[j] = (uint8_t)(ps[c] & PS_FLAGS);
+                ((uint32_t*)L.scratch)[j] = ORD_EPISODE + (uint32_t)j;
+            }
+        }
+    }
+    if (lane == 0) {
+        EnvScalars s;
+        s.t = 0;
+        s.ctr = 0;
+        s.total = 0.0;
+        p.es[e] = s;
+        done[e] = 0;
+    }
+    wave_sync();
+    const uint8_t* grid = p.grids + md.grid_off;
+    float* idq_e = idq ? idq + (size_t)e * A * 6 * H * W : nullptr;
+    float* qst_e = qst ? qst + (size_t)e * 7 * oh * ow : nullptr;
+    const bool fast = (H * W) % 4 == 0 && oh == H && ow == W && (((uintptr_t)idq_e | (uintptr_t)qst_e) & 15) == 0;
+    auto run = [&](const auto& trk) {
+        alt_prepare(trk, H * W, W, A, 0, cell, 0, AL);
+        if (fast) {
+            alt_bits(p.gridbits + md.bits_off, H * W, AL);
+            alt_emit_fast(trk, H, W, AL, cell, 0, A, idq_e, qst_e);
+            return;
+        }
+        if (idq) alt_emit_idq(trk, grid, H, W, AL, cell, 0, 0, A, true, idq_e);
+        if (qst) alt_emit_qmix(grid, H, W, AL, oh, ow, qst_e);
+    };
+    if (STALE) {
+        TrkStale trk{L.pst, L.pk, (const uint32_t*)L.scratch, P};
+        run(trk);
+    } else {
+        TrkFresh trk{L.pk, L.pst, P};
+        run(trk);
+    }
+}
+
 // The same builders on packed dict views (one agent index per view).
 __global__ __launch_bounds__(256) void k_views_alt(DevParams p, const int32_t* __restrict__ views,
                                                    const int64_t* __restrict__ offs, int n,
@@ -2164,6 +2271,24 @@ hipError_t launch_alt_transition(const DevParams& p, const uint8_t* acts, int fm
     else
         hipLaunchKernelGGL(k_alt_transition<false>, dim3(blocks_for(p.E, wpb)), dim3(256), lds * wpb, s, p, acts, fmt,
                            ops_are_ints, mask, pr, pt, r_idq, idq, qst, oh, ow, wpb, (int)lds);
+    return hipGetLastError();
+}
+
+size_t cycle_begin_lds(int P, int HW) { return reset_lds_bytes(P) + alt_lds_bytes(HW); }
+
+hipError_t launch_cycle_begin(const DevParams& p, uint8_t* done, uint8_t* completed, double* c_return,
+                              int32_t* c_steps, float* idq, float* qst, int oh, int ow, int wpb, size_t lds,
+                              hipStream_t s) {
+    const dim3 g(blocks_for(p.E, wpb)), b(256);
+    with_int<1, 2, 4, 8, 16>(nch_for(p.P), [&](auto nch) {   // the package chunks, as launch_reset picks them
+        constexpr int NCH = decltype(nch)::value;
+        if (p.stale)
+            hipLaunchKernelGGL((k_cycle_begin<true, NCH>), g, b, lds * wpb, s, p, done, completed, c_return, c_steps,
+                               idq, qst, oh, ow, wpb, (int)lds);
+        else
+            hipLaunchKernelGGL((k_cycle_begin<false, NCH>), g, b, lds * wpb, s, p, done, completed, c_return, c_steps,
+                               idq, qst, oh, ow, wpb, (int)lds);
+    });
     return hipGetLastError();
 }
 

@@ -138,6 +138,11 @@ hipError_t launch_alt_transition(const DevParams& p, const uint8_t* acts, int fm
                                  const uint8_t* mask, void* pre, double* r_idq, float* idq, float* qst, int oh, int ow,
                                  int wpb, size_t lds, hipStream_t s);
 size_t alt_pre_size(int E, int A);
+// k_cycle_begin over all p.E envs: the masked reset and the observations of the reset rows
+hipError_t launch_cycle_begin(const DevParams& p, uint8_t* done, uint8_t* completed, double* c_return,
+                              int32_t* c_steps, float* idq, float* qst, int oh, int ow, int wpb, size_t lds,
+                              hipStream_t s);
+size_t cycle_begin_lds(int P, int HW);
 size_t alt_obs_lds(int P, int HW);
 size_t views_alt_lds(int NSmax, int HW);
 

@@ -11,6 +11,7 @@
 //             operation order as the reference's torch expressions
 //   k_replay_rank / k_replay_copy  one step's ReplayBuffer.add calls   IDQ/trainer.py:304-311
 //             (a compacting append to the transition ring, cursor on the device)
+//   k_replay_copy_joint / k_replay_advance  one step's joint rows   qmix/networks.py:155-198
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -121,14 +122,15 @@ __global__ __launch_bounds__(256) void k_gae(const float* __restrict__ r, const 
 // (u < epsilon, u a 24-bit uniform in [0, 1)), x1 picks the k-th available action of an exploring
 // row, k = (x1 * n_avail) >> 32.  Any other row takes the first index among the available actions
 // with the largest q (compare `>`: a NaN never wins while the row has an available number).  A row
-// with no available action gets 0.
+// with no available action gets 0.  explored (nullable): 1 for a row that explored, else 0.
 // eps_dev / off_dev (graph-capturable form): epsilon = *eps_dev, offset = *off_dev + off_lo|off_hi<<32.
 __global__ __launch_bounds__(256) void k_select_eps(const float* __restrict__ q, const uint8_t* __restrict__ avail,
                                                     int64_t n_rows, int n_act, float epsilon, uint32_t k0,
                                                     uint32_t k1, uint32_t off_lo, uint32_t off_hi,
                                                     const float* __restrict__ eps_dev,
                                                     const uint64_t* __restrict__ off_dev,
-                                                    uint8_t* __restrict__ actions) {
+                                                    uint8_t* __restrict__ actions,
+                                                    uint8_t* __restrict__ explored) {
     const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (row >= n_rows) return;
     if (off_dev) {
@@ -155,7 +157,8 @@ __global__ __launch_bounds__(256) void k_select_eps(const float* __restrict__ q,
         }
     }
     int a = best < 0 ? 0 : best;
-    if (u < epsilon && n_avail > 0) {
+    const bool explore = u < epsilon && n_avail > 0;
+    if (explore) {
         int k = (int)(((uint64_t)c[1] * (uint64_t)n_avail) >> 32);
         for (int i = 0; i < n_act; i++) {
             if (av && !av[i]) continue;
@@ -166,6 +169,7 @@ __global__ __launch_bounds__(256) void k_select_eps(const float* __restrict__ q,
         }
     }
     actions[row] = (uint8_t)a;
+    if (explored) explored[row] = explore ? 1 : 0;
 }
 
 __global__ void k_counter_add(uint64_t* __restrict__ c, uint64_t v) {
@@ -260,6 +264,60 @@ __global__ __launch_bounds__(256) void k_replay_copy(const uint8_t* __restrict__
     }
 }
 
+// ---- the qmix/ trainer's joint replay ring (ReplayBuffer.add, qmix/networks.py:155-198): every env
+// adds one joint row per step, in env order, so row e of the step goes to slot (ptr + e) % capacity.
+struct JointRows {   // one step's rows, or the ring
+    float *state, *next_state, *obs, *next_obs;
+};
+
+template <bool VEC>
+__device__ __forceinline__ void copy_row(const float* __restrict__ src, float* __restrict__ dst, int64_t n,
+                                         int lane) {
+    if (VEC) {
+        const float4* s4 = reinterpret_cast<const float4*>(src);
+        float4* d4 = reinterpret_cast<float4*>(dst);
+        for (int64_t k = lane; k < n / 4; k += 64) d4[k] = s4[k];
+    } else {
+        for (int64_t k = lane; k < n; k += 64) dst[k] = src[k];
+    }
+}
+
+// k_replay_copy_joint, one wave per env.  It only reads the cursor (k_replay_advance moves it, in a
+// launch of its own).  Of a step with more envs than the ring has slots only the last `capacity`
+// rows are written (what the sequential adds leave), so no two waves write one slot.  VEC: rows as
+// 16-byte vectors.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_replay_copy_joint(int E, int A, int64_t state_floats, int64_t obs_floats,
+                                                           JointRows in, const uint8_t* __restrict__ actions,
+                                                           const double* __restrict__ reward,
+                                                           const uint8_t* __restrict__ done, int64_t capacity,
+                                                           const int64_t* __restrict__ cursor, JointRows ring,
+                                                           int64_t* __restrict__ ring_action,
+                                                           float* __restrict__ ring_reward,
+                                                           uint8_t* __restrict__ ring_done) {
+    const int lane = threadIdx.x & 63;
+    const int e = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (e >= E || (int64_t)e < (int64_t)E - capacity) return;
+    const int64_t slot = (cursor[0] + e) % capacity;
+    copy_row<VEC>(in.state + (int64_t)e * state_floats, ring.state + slot * state_floats, state_floats, lane);
+    copy_row<VEC>(in.next_state + (int64_t)e * state_floats, ring.next_state + slot * state_floats, state_floats, lane);
+    copy_row<VEC>(in.obs + (int64_t)e * obs_floats, ring.obs + slot * obs_floats, obs_floats, lane);
+    copy_row<VEC>(in.next_obs + (int64_t)e * obs_floats, ring.next_obs + slot * obs_floats, obs_floats, lane);
+    if (lane < A) ring_action[slot * A + lane] = (int64_t)actions[(int64_t)e * A + lane];   // A <= 64 lanes
+    if (lane == 0) {
+        ring_reward[slot] = (float)reward[e];   // fp64 -> float32, rounded once
+        ring_done[slot] = done[e];
+    }
+}
+
+__global__ void k_replay_advance(int64_t* __restrict__ cursor, int64_t rows, int64_t capacity) {
+    if (threadIdx.x == 0) {
+        const int64_t ptr = cursor[0], size = cursor[1];
+        cursor[0] = (ptr + rows) % capacity;
+        cursor[1] = size + rows < capacity ? size + rows : capacity;
+    }
+}
+
 }  // namespace mdl
 
 namespace {
@@ -303,7 +361,7 @@ int mdl_sample_actions_dev(const float* logits, int64_t n_rows, int32_t n_action
 
 static int select_eps(const char* what, const float* q, const uint8_t* avail, int64_t n_rows, int32_t n_actions,
                       float epsilon, uint64_t seed, uint64_t offset, const float* epsilon_dev,
-                      const uint64_t* offset_dev, uint8_t* actions, void* stream) {
+                      const uint64_t* offset_dev, uint8_t* actions, uint8_t* explored, void* stream) {
     char msg[96];
     if (!q || !actions) {
         snprintf(msg, sizeof msg, "%s: null argument", what);
@@ -317,7 +375,7 @@ static int select_eps(const char* what, const float* q, const uint8_t* avail, in
     const int64_t blocks = (n_rows + 255) / 256;
     hipLaunchKernelGGL(mdl::k_select_eps, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, q, avail, n_rows,
                        (int)n_actions, epsilon, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)offset,
-                       (uint32_t)(offset >> 32), epsilon_dev, offset_dev, actions);
+                       (uint32_t)(offset >> 32), epsilon_dev, offset_dev, actions, explored);
     const hipError_t e = hipGetLastError();
     if (e == hipSuccess) return 0;
     snprintf(msg, sizeof msg, "%s: launch failed", what);
@@ -327,7 +385,7 @@ static int select_eps(const char* what, const float* q, const uint8_t* avail, in
 int mdl_select_actions_eps(const float* q, const uint8_t* avail, int64_t n_rows, int32_t n_actions, float epsilon,
                            uint64_t seed, uint64_t offset, uint8_t* actions, void* stream) {
     return select_eps("mdl_select_actions_eps", q, avail, n_rows, n_actions, epsilon, seed, offset, nullptr, nullptr,
-                      actions, stream);
+                      actions, nullptr, stream);
 }
 
 int mdl_select_actions_eps_dev(const float* q, const uint8_t* avail, int64_t n_rows, int32_t n_actions,
@@ -335,7 +393,23 @@ int mdl_select_actions_eps_dev(const float* q, const uint8_t* avail, int64_t n_r
                                uint64_t offset_add, uint8_t* actions, void* stream) {
     if (!epsilon_dev || !offset_dev) return rfail("mdl_select_actions_eps_dev: null argument");
     return select_eps("mdl_select_actions_eps_dev", q, avail, n_rows, n_actions, 0.0f, seed, offset_add, epsilon_dev,
-                      offset_dev, actions, stream);
+                      offset_dev, actions, nullptr, stream);
+}
+
+int mdl_select_actions_eps_mark(const float* q, const uint8_t* avail, int64_t n_rows, int32_t n_actions,
+                                float epsilon, uint64_t seed, uint64_t offset, uint8_t* actions, uint8_t* explored,
+                                void* stream) {
+    if (!explored) return rfail("mdl_select_actions_eps_mark: null argument");
+    return select_eps("mdl_select_actions_eps_mark", q, avail, n_rows, n_actions, epsilon, seed, offset, nullptr,
+                      nullptr, actions, explored, stream);
+}
+
+int mdl_select_actions_eps_mark_dev(const float* q, const uint8_t* avail, int64_t n_rows, int32_t n_actions,
+                                    const float* epsilon_dev, uint64_t seed, const uint64_t* offset_dev,
+                                    uint64_t offset_add, uint8_t* actions, uint8_t* explored, void* stream) {
+    if (!epsilon_dev || !offset_dev || !explored) return rfail("mdl_select_actions_eps_mark_dev: null argument");
+    return select_eps("mdl_select_actions_eps_mark_dev", q, avail, n_rows, n_actions, 0.0f, seed, offset_add,
+                      epsilon_dev, offset_dev, actions, explored, stream);
 }
 
 int mdl_counter_add(uint64_t* counter, uint64_t value, void* stream) {
@@ -371,6 +445,38 @@ int mdl_replay_append(const uint8_t* filled, int32_t E, int32_t A, int64_t row_f
                            ring_reward, ring_done);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : rfail("mdl_replay_append: launch failed", e);
+}
+
+int mdl_replay_append_joint(int32_t E, int32_t A, int64_t state_floats, int64_t obs_floats, const float* state,
+                            const float* next_state, const float* obs, const float* next_obs, const uint8_t* actions,
+                            const double* reward, const uint8_t* done, int64_t capacity, int64_t* cursor,
+                            float* ring_state, float* ring_next_state, float* ring_obs, float* ring_next_obs,
+                            int64_t* ring_action, float* ring_reward, uint8_t* ring_done, void* stream) {
+    if (!state || !next_state || !obs || !next_obs || !actions || !reward || !done || !cursor || !ring_state ||
+        !ring_next_state || !ring_obs || !ring_next_obs || !ring_action || !ring_reward || !ring_done)
+        return rfail("mdl_replay_append_joint: null argument");
+    if (E < 0 || A < 1 || A > MDL_MAX_ROBOTS || state_floats < 1 || obs_floats < 1 || capacity < 1)
+        return rfail("mdl_replay_append_joint: bad sizes");
+    if (E == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t row = (int64_t)A * obs_floats;   // one joint observation row: every agent's
+    const uintptr_t all = (uintptr_t)state | (uintptr_t)next_state | (uintptr_t)obs | (uintptr_t)next_obs |
+                          (uintptr_t)ring_state | (uintptr_t)ring_next_state | (uintptr_t)ring_obs |
+                          (uintptr_t)ring_next_obs;
+    const bool vec = state_floats % 4 == 0 && row % 4 == 0 && (all & 15) == 0;
+    const mdl::JointRows in{const_cast<float*>(state), const_cast<float*>(next_state), const_cast<float*>(obs),
+                            const_cast<float*>(next_obs)};
+    const mdl::JointRows ring{ring_state, ring_next_state, ring_obs, ring_next_obs};
+    const dim3 g((unsigned)((E + 3) / 4)), b(256);
+    if (vec)
+        hipLaunchKernelGGL(mdl::k_replay_copy_joint<true>, g, b, 0, s, (int)E, (int)A, state_floats, row, in, actions,
+                           reward, done, capacity, (const int64_t*)cursor, ring, ring_action, ring_reward, ring_done);
+    else
+        hipLaunchKernelGGL(mdl::k_replay_copy_joint<false>, g, b, 0, s, (int)E, (int)A, state_floats, row, in, actions,
+                           reward, done, capacity, (const int64_t*)cursor, ring, ring_action, ring_reward, ring_done);
+    hipLaunchKernelGGL(mdl::k_replay_advance, dim3(1), dim3(64), 0, s, cursor, (int64_t)E, capacity);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : rfail("mdl_replay_append_joint: launch failed", e);
 }
 
 int mdl_gae(const float* rewards, const float* values, const float* next_value, const uint8_t* dones, int32_t T,

@@ -103,6 +103,13 @@ SIGNATURES = {
     "mdl_sample_actions_dev": (C.c_int, [_vp, C.c_int64, _i32, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp]),
     "mdl_select_actions_eps": (C.c_int, [_vp, _vp, C.c_int64, _i32, C.c_float, C.c_uint64, C.c_uint64, _vp, _vp]),
     "mdl_select_actions_eps_dev": (C.c_int, [_vp, _vp, C.c_int64, _i32, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp]),
+    "mdl_select_actions_eps_mark": (C.c_int, [_vp, _vp, C.c_int64, _i32, C.c_float, C.c_uint64, C.c_uint64, _vp, _vp,
+                                              _vp]),
+    "mdl_select_actions_eps_mark_dev": (C.c_int, [_vp, _vp, C.c_int64, _i32, _vp, C.c_uint64, _vp, C.c_uint64, _vp,
+                                                  _vp, _vp]),
+    "mdl_cycle_begin": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
+    "mdl_replay_append_joint": (C.c_int, [_i32, _i32, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                          C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mdl_counter_add": (C.c_int, [_vp, C.c_uint64, _vp]),
     "mdl_replay_append": (C.c_int, [_vp, _i32, _i32, C.c_int64, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp,
                                     _vp, _vp, _vp, _vp]),

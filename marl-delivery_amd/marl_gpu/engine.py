@@ -561,6 +561,43 @@ class BatchedEnv:
         self._keep = (None, actions)
         return r_out, {k: v for k, v in p.items() if v is not None}
 
+    def cycle_begin(self, done: torch.Tensor, out: dict | None = None, completed: torch.Tensor | None = None,
+                    completed_return: torch.Tensor | None = None, completed_steps: torch.Tensor | None = None,
+                    state_shape=None):
+        """The lazy reset that opens a time step of the map-QMIX cycle (qmix/trainer.py:329-346), one
+        launch over all E envs.  An env whose byte of ``done`` (uint8 [E], read and cleared on the
+        device) is set reports its finished episode -- completed[e] = 1, completed_return[e] = its
+        total_reward, completed_steps[e] = its t --, has its tracker emptied and is reset (exactly
+        ``clear_tracker(ids)`` then ``reset(ids)``), and rows e of ``out["idq_obs"]`` /
+        ``out["qmix_state"]`` receive ``build_obs_alt``'s observations of the new state.  Any other
+        env gets completed 0, return 0.0, steps 0 and keeps its state and its rows.  ``out`` holds the
+        caller's tensors (either may be missing); completed uint8, completed_return float64,
+        completed_steps int32, each [E] or None.  Returns ``out``."""
+        n = self.E
+        if self._shape_run_end[0] < n:
+            raise ValueError("cycle_begin: the envs mix map shapes (build one engine per map shape)")
+        H, W = self.grids[int(self.env_map[0])].shape
+        oh, ow = (H, W) if state_shape is None else (int(state_shape[1]), int(state_shape[2]))
+        self._check_mask(done, "done")
+        out = {} if out is None else out
+        if out.get("idq_obs") is not None:
+            self._check_obs_out(out["idq_obs"], "idq_obs", (n, self.A, 6, H, W))
+        if out.get("qmix_state") is not None:
+            self._check_obs_out(out["qmix_state"], "qmix_state", (n, 7, oh, ow))
+        if completed is not None:
+            self._check_mask(completed, "completed")
+            if completed.data_ptr() == done.data_ptr():
+                raise ValueError("completed must not be the done mask itself (the launch reads one and writes both)")
+        for t, dt, name in ((completed_return, torch.float64, "completed_return"),
+                            (completed_steps, torch.int32, "completed_steps")):
+            if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_cuda
+                                  or t.get_device() != self.device.index or not t.is_contiguous() or t.numel() < n):
+                raise TypeError(f"{name} must be a contiguous {dt} tensor of {n} entries on {self.device}")
+        check(lib().mdl_cycle_begin(self._h, done.data_ptr(), ptr(completed), ptr(completed_return),
+                                    ptr(completed_steps), ptr(out.get("idq_obs")), ptr(out.get("qmix_state")),
+                                    oh, ow, self._stream()), "mdl_cycle_begin")
+        return out
+
     # ---- greedy baseline (SURVEY.md §8(f)3): greedyagent.py batched on the device ----
     def greedy_init(self, env_ids=None):
         """``GreedyAgents()`` + ``init_agents(state)`` for the listed envs (right after their reset)."""

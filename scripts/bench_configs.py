@@ -14,6 +14,8 @@
                     step against the host-driven subset loop
   --idq             IDQ transition collection: alt_transition against build_obs_alt, and one collector
                     step against the host-driven loop it replaces
+  --qmix-cycle      map-QMIX cycle collection: cycle_begin against reset + build_obs_alt, the joint
+                    replay append, and one collector step against the host-driven loop
 
 Prints one JSON line per config with per-kernel HIP-event times and the
 algorithmic-bytes roofline of SURVEY.md §8(d).
@@ -552,6 +554,163 @@ def run_idq(steps):
         ref.close()
 
 
+def run_qmix_cycle(steps):
+    """map-QMIX cycle collection ("map-QMIX cycle collection"); map1, A=5, P=20, fresh
+    tracker, 4 and 4,096 envs, T = 50 with the episodes staggered by initial marks (env e is marked
+    at warm-up step e % T), so the resets spread over the steps.  hipGraphs of G calls, five
+    interleaved repeats each.
+
+    1. ``cycle_begin`` with an all-zero mask; ``cycle_begin`` with every env marked against
+       ``reset`` + ``build_obs_alt`` as two launches (both behind the same ``fill_`` of the mask).
+    2. ``JointReplay.add`` alone, with the bytes it moves (from the shapes) and GB/s.
+    3. One ``QmixCycleCollector`` step (the agent's forward replaced by preset Q-values), eager
+       and graph-replayed, against the host-driven loop it replaces: done flags read back, the id
+       list built on the host, ``clear_tracker`` / ``reset(ids)``, ``build_obs_alt``, torch index
+       copies into a ring.
+    """
+    import marl_gpu
+    from marl_gpu.maps import grid_array, load_map, map_path
+    from marl_gpu.qmix_cycle import JointReplay, QmixCycleCollector
+    g1 = grid_array(load_map(map_path("map1.txt")))
+    H, W = g1.shape
+    A, P, T, G, cap = 5, 20, 50, 50, 8192
+    dev = torch.device("cuda", 0)
+    gen = torch.Generator(device=dev).manual_seed(0)
+    reps = max(2, steps // G)
+
+    def many(fn):
+        def f():
+            for _ in range(G):
+                fn()
+        return f
+
+    for E in (4, 4096):
+        env = marl_gpu.BatchedEnv(g1, E, A, P, T, seed=42, tracker="fresh")
+        ref = marl_gpu.BatchedEnv(g1, E, A, P, T, seed=42, tracker="fresh")
+        q = torch.randn(E * A, 15, generator=gen, device=dev)
+        agent = lambda o: q   # noqa: E731  (stand-in for the network's forward)
+        rep = JointReplay(cap, A, (6, H, W), (7, H, W), device=dev)
+        col = QmixCycleCollector(env, rep, seed=1)
+        col.begin()
+        for k in range(T):                              # stagger the episodes
+            col.done[k::T] = 1
+            col.step(agent, 0.2)
+
+        # 1. cycle_begin alone (on `ref`, which the collector does not use)
+        ref.reset()
+        out = {"idq_obs": torch.zeros((E, A, 6, H, W), dtype=torch.float32, device=dev),
+               "qmix_state": torch.zeros((E, 7, H, W), dtype=torch.float32, device=dev)}
+        mask = torch.zeros(E, dtype=torch.uint8, device=dev)
+        comp = torch.zeros(E, dtype=torch.uint8, device=dev)
+        cret = torch.zeros(E, dtype=torch.float64, device=dev)
+        cst = torch.zeros(E, dtype=torch.int32, device=dev)
+
+        def begin_zero():
+            ref.cycle_begin(mask, out=out, completed=comp, completed_return=cret, completed_steps=cst)
+
+        def begin_all():
+            mask.fill_(1)
+            ref.cycle_begin(mask, out=out, completed=comp, completed_return=cret, completed_steps=cst)
+
+        def two_launches():
+            mask.fill_(1)
+            ref.reset()
+            ref.build_obs_alt(out=out)
+
+        gz, ga, g2 = _graph_of(many(begin_zero)), _graph_of(many(begin_all)), _graph_of(many(two_launches))
+        tz, ta, t2 = [], [], []
+        for _ in range(5):
+            tz.append(_replay_us(gz, reps, G))
+            ta.append(_replay_us(ga, reps, G))
+            t2.append(_replay_us(g2, reps, G))
+        print(json.dumps({"config": "qmix_cycle_begin", "envs": E, "agents": A, "packages": P, "graph_calls": G,
+                          "replays": reps, "cycle_begin_zero_mask_us": tz, "cycle_begin_all_marked_us": ta,
+                          "reset_plus_build_obs_alt_us": t2,
+                          "note": "us per call; the marked and the two-launch figures include one fill_ of the mask"}),
+              flush=True)
+
+        # 2. the append alone
+        # Four source sets taken in turn and a ring of 16 steps: at 4,096 envs a step reads 121 MB and
+        # writes 121 MB, so neither the sources (485 MB) nor the ring (1.9 GB) fit the 256 MB
+        # Infinity Cache and the GB/s figure is HBM traffic.
+        NS, cap2 = 4, 16 * max(E, 4)
+        f32 = dict(dtype=torch.float32, device=dev)
+        src = [(torch.zeros((E, 7, H, W), **f32), torch.zeros((E, 7, H, W), **f32),
+                torch.zeros((E, A, 6, H, W), **f32), torch.zeros((E, A, 6, H, W), **f32)) for _ in range(NS)]
+        u = torch.zeros((E, A), dtype=torch.uint8, device=dev)
+        rw = torch.zeros(E, dtype=torch.float64, device=dev)
+        dn = torch.zeros(E, dtype=torch.uint8, device=dev)
+        ring2 = JointReplay(cap2, A, (6, H, W), (7, H, W), device=dev)
+
+        def adds():
+            for k in range(G):
+                s1, s2, o1, o2 = src[k % NS]
+                ring2.add(s1, s2, o1, o2, u, rw, dn)
+
+        gadd = _graph_of(adds)
+        tadd = [_replay_us(gadd, reps, G) for _ in range(5)]
+        row = 2 * (7 * H * W + A * 6 * H * W) * 4
+        moved = E * (2 * row + A * (1 + 8) + (8 + 4) + (1 + 1))        # read + written, from the shapes
+        print(json.dumps({"config": "qmix_joint_add", "envs": E, "agents": A, "capacity": cap2, "source_sets": NS,
+                          "graph_calls": G, "replays": reps, "add_us": tadd, "bytes_moved": moved,
+                          "gb_per_s": [moved / (t * 1e-6) / 1e9 for t in tadd]}), flush=True)
+        del ring2, gadd, src
+
+        # 3. one collector step against the host-driven loop
+        ring = JointReplay(cap, A, (6, H, W), (7, H, W), device=dev)   # only its tensors: written by torch indexing
+        ob = [torch.zeros((E, A, 6, H, W), dtype=torch.float32, device=dev) for _ in range(2)]
+        sb = [torch.zeros((E, 7, H, W), dtype=torch.float32, device=dev) for _ in range(2)]
+        st = {"done": torch.zeros(E, dtype=torch.uint8, device=dev), "ptr": 0, "cur": 0}
+        r_env = torch.zeros(E, dtype=torch.float64, device=dev)
+        r_sh = torch.zeros(E, dtype=torch.float32, device=dev)
+        a_all = q.view(E, A, 15)[:, :, 0].gt(0).to(torch.uint8).contiguous()   # stand-in actions
+        ar = torch.arange(E, device=dev)
+
+        def host_step(k):
+            c = st["cur"]
+            idx = np.nonzero(st["done"].cpu().numpy())[0]                              # done flags read back
+            if idx.size:
+                ref.clear_tracker(idx)
+                ref.reset(idx)
+                ref.build_obs_alt(out={"idq_obs": ob[c], "qmix_state": sb[c]})        # the reset rows (all rebuilt)
+            ref.step(a_all, auto_reset=False, out=(r_env, r_sh, st["done"]))
+            ref.build_obs_alt(out={"idq_obs": ob[1 - c], "qmix_state": sb[1 - c]})
+            slots = (ar + st["ptr"]) % cap                                             # the ring writes
+            ring.states[slots] = sb[c]
+            ring.next_states[slots] = sb[1 - c]
+            ring.observations[slots] = ob[c]
+            ring.next_observations[slots] = ob[1 - c]
+            ring.actions[slots] = a_all.long()
+            ring.total_reward[slots, 0] = r_env.float()
+            ring.dones[slots, 0] = st["done"]
+            st["ptr"] = (st["ptr"] + E) % cap
+            st["cur"] = 1 - c
+
+        ref.reset()
+        ref.build_obs_alt(out={"idq_obs": ob[0], "qmix_state": sb[0]})
+        for k in range(T):                              # the same stagger, and torch's indexing kernels once
+            st["done"][k::T] = 1
+            host_step(k)
+        col.cycle(agent, 0.2, G, graph=True)            # eager run + capture
+        col.cycle(agent, 0.2, G, graph=True)
+        te, tg, th = [], [], []
+        for _ in range(5):
+            te.append(timed(lambda k: col.step(agent, 0.2), G))
+            tg.append(timed(lambda k: col.cycle(agent, 0.2, G, graph=True), reps) / G)
+            th.append(timed(host_step, G))
+        assert len(col._graphs) >= 1
+        print(json.dumps({"config": "qmix_cycle_step", "envs": E, "agents": A, "packages": P, "steps": G,
+                          "max_time_steps": T, "collector_step_graph_us": tg, "collector_step_eager_us": te,
+                          "host_loop_step_us": th,
+                          "launches": {"collector": "k_cycle_begin, k_select_eps, k_step, k_alt_obs, k_replay_copy_joint, "
+                                                    "k_replay_advance; no copy, no sync",
+                                       "host_loop": "one D2H copy and sync per step, k_reset and k_alt_obs for the "
+                                                    "reset envs, k_step, k_alt_obs, the torch scatter kernels"}}),
+              flush=True)
+        env.close()
+        ref.close()
+
+
 def run_config1(seconds=5.0):
     """BASELINE.json configs[0]: map1, 5 agents, ONE env, a random agent driving the dict
     API (randomagent.py: np.random.choice over moves and ops per robot) -- plumbing, not a
@@ -589,6 +748,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--qmix", action="store_true", help="the QMIX episode-collection measurements only")
     ap.add_argument("--idq", action="store_true", help="the IDQ transition-collection measurements only")
+    ap.add_argument("--qmix-cycle", action="store_true", help="the map-QMIX cycle-collection measurements only")
     a = ap.parse_args()
     torch.cuda.set_device(0)
     if a.qmix:
@@ -596,6 +756,9 @@ def main():
         return
     if a.idq:
         run_idq(a.steps)
+        return
+    if a.qmix_cycle:
+        run_qmix_cycle(a.steps)
         return
     for c in a.config.split(","):
         if c == "1":
