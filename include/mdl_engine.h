@@ -238,6 +238,32 @@ int mdl_cycle_begin(MdlEngine* eng, uint8_t* done, uint8_t* completed, double* c
 int mdl_greedy_init(MdlEngine* eng, const int32_t* env_ids, int32_t n, void* stream);
 int mdl_greedy_actions(MdlEngine* eng, const int32_t* env_ids, int32_t n, uint8_t* actions, void* stream);
 
+/* mdl_greedy_actions for an episode batch whose running-env mask lives on the device (the greedy
+ * loop of evaluation.py:28-47 over E envs at once, with no host round trip): the full batch, row e =
+ * env e, actions uint8 [E][A] in MDL_ACTION_CODES.
+ * active: DEVICE uint8 [E], the caller's (mdl_step_episode's mask), read and never written.
+ *   active[e] != 0: exactly mdl_greedy_actions on env e -- the action bytes and the agent record
+ *     afterwards are bit for bit the same.
+ *   active[e] == 0: actions[e][0..A) = 0, i.e. ('S', '0'); nothing else of env e is read or written,
+ *     its agent record included (get_actions appends the spawns of this t to the record, so a skipped
+ *     env's record must stay as it is).  The env's wave reads its mask byte and leaves.
+ *   active == NULL: mdl_greedy_actions(eng, NULL, E, actions, stream).
+ * Preconditions and errors are mdl_greedy_actions': mdl_greedy_init has run, and after mdl_load_state
+ * of a checkpoint without greedy records only mdl_greedy_init without an id list makes it usable
+ * again.  Mixed map shapes are allowed.  One launch (mdl_greedy_actions' kernel with the mask
+ * pointer), no allocation; captures into a hipGraph. */
+int mdl_greedy_actions_masked(MdlEngine* eng, const uint8_t* active, uint8_t* actions, void* stream);
+
+/* What an evaluation reads of each env's episode (evaluation.py:49-51), without mdl_read_state's
+ * tables: DEVICE outputs [E], row e = env e, any of them may be NULL.
+ *   total_reward f64  the env's total_reward: the same bits mdl_read_state returns
+ *   delivered    i32  the number of package slots j < P whose status is delivered
+ *                     (sum(1 for p in env.packages if p.status == 'delivered'); == the count of
+ *                     status 3 in mdl_read_state's pkgs[e][:][7])
+ *   steps        i32  t
+ * One launch, one wave per env; touches no state and the engine gains none.  Captures into a hipGraph. */
+int mdl_episode_results(MdlEngine* eng, double* total_reward, int32_t* delivered, int32_t* steps, void* stream);
+
 /* ---- dict-API mailbox: the per-call path of Environment.step / reset on single envs ----
  * Environment.step (env.py:173-306) and VectorizedEnv.step / reset(indices) (QMIX/env_vectorized.py:13-37)
  * return Python dicts per call, so their cost is the host <-> GPU round trip, not the step.  The mailbox

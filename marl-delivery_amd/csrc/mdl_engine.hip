@@ -935,6 +935,25 @@ int mdl_greedy_actions(MdlEngine* eng, const int32_t* env_ids, int32_t n, uint8_
     return 0;
 }
 
+int mdl_greedy_actions_masked(MdlEngine* eng, const uint8_t* active, uint8_t* actions, void* stream) {
+    if (!eng || !actions) return fail("mdl_greedy_actions_masked: null argument");
+    if (!eng->gstate) return fail("mdl_greedy_actions_masked: call mdl_greedy_init first");
+    if (eng->greedy_stale)
+        return fail("mdl_greedy_actions_masked: the greedy agents' state predates mdl_load_state of a checkpoint "
+                    "without it; call mdl_greedy_init without an id list");
+    DeviceGuard dg(eng->device);
+    HIPCHK(mdl::launch_greedy_act(eng->p, eng->glay, eng->gstate, eng->gtab, nullptr, eng->p.E, actions,
+                                  (hipStream_t)stream, active));
+    return 0;
+}
+
+int mdl_episode_results(MdlEngine* eng, double* total_reward, int32_t* delivered, int32_t* steps, void* stream) {
+    if (!eng) return fail("mdl_episode_results: null engine");
+    DeviceGuard dg(eng->device);
+    HIPCHK(mdl::launch_episode_results(eng->p, total_reward, delivered, steps, (hipStream_t)stream));
+    return 0;
+}
+
 // ---- checkpoint ----
 namespace {
 constexpr uint32_t CKPT_VERSION = 2;

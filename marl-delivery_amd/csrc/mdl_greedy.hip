@@ -6,6 +6,7 @@
 //                  LDS; table[goal][cell] u16 (0xffff = not reached)
 //   k_greedy_init  GreedyAgents() + init_agents(state)      greedyagent.py:44-64
 //   k_greedy_act   get_actions(state) -> action codes       greedyagent.py:104-170
+//                  (with a mask: only for the envs whose episode still runs)
 //
 // The agent is restated bug for bug (the test suite checks it action for action):
 // the package list holds each t=0 spawn twice (init_agents and the first
@@ -116,9 +117,12 @@ __global__ __launch_bounds__(256) void k_greedy_init(DevParams p, GreedyLayout g
 
 // One get_actions(state) per env; actions[w][a] = move code | op << 3 (MDL_ACTION_CODES).
 // The env's list and free flags are staged in its wave's LDS slice (list u16[cap], free u8[cap]).
+// mask (nullable, uint8 [E], only without env_ids): an env whose byte is 0 gets the all-zero row
+// ('S', '0') and its wave leaves before it loads anything of the env or of its agent record.
 __global__ __launch_bounds__(256) void k_greedy_act(DevParams p, GreedyLayout g, unsigned char* __restrict__ gs,
                                                     const uint16_t* __restrict__ tables, const int* __restrict__ env_ids,
-                                                    int n, uint8_t* __restrict__ actions) {
+                                                    int n, uint8_t* __restrict__ actions,
+                                                    const uint8_t* __restrict__ mask) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int wave = wave_id();
     const int w = blockIdx.x * 4 + wave;
@@ -126,6 +130,10 @@ __global__ __launch_bounds__(256) void k_greedy_act(DevParams p, GreedyLayout g,
     const int e = env_ids ? env_ids[w] : w;
     if ((unsigned)e >= (unsigned)p.E) return;
     const int lane = lane_id();
+    if (mask && mask[e] == 0) {
+        if (lane < p.A) actions[(size_t)w * p.A + lane] = 0;
+        return;
+    }
     const int A = p.A, P = p.P, cap = g.cap;
     uint16_t* list = (uint16_t*)(smem + (size_t)wave * g.lds_stride);
     uint8_t* free_ = (uint8_t*)(list + cap);
@@ -263,9 +271,9 @@ hipError_t launch_greedy_init(const DevParams& p, const GreedyLayout& g, unsigne
 }
 
 hipError_t launch_greedy_act(const DevParams& p, const GreedyLayout& g, unsigned char* gs, const uint16_t* tables,
-                             const int* ids, int n, uint8_t* actions, hipStream_t s) {
+                             const int* ids, int n, uint8_t* actions, hipStream_t s, const uint8_t* mask) {
     hipLaunchKernelGGL(k_greedy_act, dim3((n + 3) / 4), dim3(256), 4 * (size_t)g.lds_stride, s, p, g, gs, tables, ids,
-                       n, actions);
+                       n, actions, mask);
     return hipGetLastError();
 }
 

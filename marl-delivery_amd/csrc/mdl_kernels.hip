@@ -9,6 +9,7 @@
 //                  convert_global_state for every agent         MAPPO/helper.py:6-255
 //   k_views_*      the same builders / shaping fed from packed dict views
 //   k_export       int32 snapshot of the SoA state
+//   k_episode_results  total_reward, delivered count and t per env   evaluation.py:49-51
 //
 // One wavefront per env; `wpb` envs per 256-thread workgroup, each with its
 // own LDS slice of `lds_stride` bytes (dynamic shared memory).  Waves never
@@ -1945,6 +1946,36 @@ __global__ __launch_bounds__(256) void k_export(DevParams p, int32_t* __restrict
     }
 }
 
+// ------------------------------------------------------------ episode results
+// What an evaluation reads of a finished episode (evaluation.py:49-51), without the k_export
+// tables: total_reward, the number of delivered package slots and t, one row per env.  One wave
+// per env, no workgroup barrier; the state words come in chunks of 64 slots, one per lane
+// (coalesced), and a ballot counts a chunk.  A lane past P is left out by its index: it loads
+// nothing.  Touches no state.
+__global__ __launch_bounds__(256) void k_episode_results(DevParams p, double* __restrict__ total,
+                                                         int32_t* __restrict__ delivered,
+                                                         int32_t* __restrict__ steps) {
+    const int lane = lane_id();
+    const int e = blockIdx.x * 4 + wave_id();
+    if (e >= p.E) return;
+    const int P = p.P;
+    int nd = 0;
+    if (delivered) {
+        const uint16_t* ps = p.pstate + (size_t)e * P;
+        for (int j0 = 0; j0 < P; j0 += WAVE) {
+            const int j = j0 + lane;
+            const bool dl = j < P && (ps[j] & PS_STATUS) == ST_DELIVERED;
+            nd += popc64(ballot(dl));
+        }
+    }
+    if (lane == 0) {
+        const EnvScalars s = p.es[e];
+        if (total) total[e] = s.total;
+        if (delivered) delivered[e] = nd;
+        if (steps) steps[e] = s.t;
+    }
+}
+
 // ------------------------------------------------------- dict-API mailbox export
 // The rows of the envs a dict-API call touched (row w = env ids[w], or env w without ids),
 // written straight into the engine's host-mapped mailbox (no device staging buffer, no copy
@@ -2392,6 +2423,12 @@ hipError_t launch_export(const DevParams& p, int32_t* robots, int32_t* pkgs, int
                          int32_t* tracker, int32_t* tracker_data, hipStream_t s) {
     hipLaunchKernelGGL(k_export, dim3(blocks_for(p.E, 4)), dim3(256), 0, s, p, robots, pkgs, t, total, tracker,
                        tracker_data);
+    return hipGetLastError();
+}
+
+hipError_t launch_episode_results(const DevParams& p, double* total, int32_t* delivered, int32_t* steps,
+                                  hipStream_t s) {
+    hipLaunchKernelGGL(k_episode_results, dim3(blocks_for(p.E, 4)), dim3(256), 0, s, p, total, delivered, steps);
     return hipGetLastError();
 }
 

@@ -112,6 +112,9 @@ hipError_t launch_mail_export(const DevParams& p, const int32_t* ids, int n, con
                               unsigned base, int32_t seq, hipStream_t s);
 hipError_t launch_export(const DevParams& p, int32_t* robots, int32_t* pkgs, int32_t* t, double* total,
                          int32_t* tracker, int32_t* tracker_data, hipStream_t s);
+// k_episode_results over all p.E envs: total_reward, delivered package slots, t (each may be null)
+hipError_t launch_episode_results(const DevParams& p, double* total, int32_t* delivered, int32_t* steps,
+                                  hipStream_t s);
 
 // Greedy agent record layout (mdl_greedy.hip): per env `stride` bytes.
 struct GreedyLayout {
@@ -121,8 +124,10 @@ struct GreedyLayout {
 hipError_t launch_bfs_table(const uint8_t* grid, int H, int W, uint16_t* table, hipStream_t s);
 hipError_t launch_greedy_init(const DevParams& p, const GreedyLayout& g, unsigned char* gs, const int* ids, int n,
                               hipStream_t s);
+// mask (device uint8 [E], may be null; then ids must be null and n == p.E): an env whose byte is 0
+// gets the all-zero action row and nothing else of it is read or written
 hipError_t launch_greedy_act(const DevParams& p, const GreedyLayout& g, unsigned char* gs, const uint16_t* tables,
-                             const int* ids, int n, uint8_t* actions, hipStream_t s);
+                             const int* ids, int n, uint8_t* actions, hipStream_t s, const uint8_t* mask = nullptr);
 
 hipError_t launch_alt_obs(const DevParams& p, int env_begin, int n, float* idq, float* qst, int oh, int ow, int wpb,
                           size_t lds, hipStream_t s);

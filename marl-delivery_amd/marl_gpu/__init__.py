@@ -8,11 +8,13 @@ kernels in ``libmdl.so``; there is no CPU execution path.
 """
 from ._lib import MdlError, lib
 from .engine import MAPPO_SHAPING, QMIX_SHAPING, BatchedEnv
+from .evaluate import Evaluator, random_action_tape, run_eval
 from .idq_rollout import IdqCollector, TransitionReplay
 from .qmix_cycle import JointReplay, QmixCycleCollector, select_actions_eps_mark, select_actions_eps_mark_dev
 from .qmix_rollout import EpisodeReplay, QmixCollector, select_actions_eps, select_actions_eps_dev
 
 __all__ = ["BatchedEnv", "MdlError", "MAPPO_SHAPING", "QMIX_SHAPING", "lib", "QmixCollector", "EpisodeReplay",
            "select_actions_eps", "select_actions_eps_dev", "IdqCollector", "TransitionReplay", "JointReplay",
-           "QmixCycleCollector", "select_actions_eps_mark", "select_actions_eps_mark_dev"]
+           "QmixCycleCollector", "select_actions_eps_mark", "select_actions_eps_mark_dev", "Evaluator",
+           "random_action_tape", "run_eval"]
 __version__ = "0.1.0"

@@ -90,6 +90,8 @@ SIGNATURES = {
     "mdl_views_idq_reward": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),
     "mdl_greedy_init": (C.c_int, [_vp, _vp, _i32, _vp]),
     "mdl_greedy_actions": (C.c_int, [_vp, _vp, _i32, _vp, _vp]),
+    "mdl_greedy_actions_masked": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "mdl_episode_results": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "mdl_mailbox": (C.c_int, [_vp, C.POINTER(MdlMailbox)]),
     "mdl_mail_step": (C.c_int, [_vp, _i32, _i32, _i32, _vp]),
     "mdl_mail_reset": (C.c_int, [_vp, _i32, _i32, _vp]),

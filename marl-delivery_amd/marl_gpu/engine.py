@@ -621,6 +621,48 @@ class BatchedEnv:
         self._keep_g = ids
         return out
 
+    def greedy_actions_masked(self, active, out=None) -> torch.Tensor:
+        """``greedy_actions()`` for an episode batch: uint8 [E, A] in the "codes" format, row e = env e.
+        An env whose byte of ``active`` (uint8 [E] on the device, ``step_episode``'s mask; read, never
+        written) is 0 gets the all-zero row ('S', '0') and is not touched -- its agent record stays as
+        it is.  ``active=None``: every env, exactly ``greedy_actions()``.  One launch, no host round trip."""
+        if active is not None:
+            self._check_mask(active, "active")
+        if out is None:
+            out = torch.empty((self.E, self.A), dtype=torch.uint8, device=self.device)
+        elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or not out.is_cuda \
+                or not out.is_contiguous() or out.numel() < self.E * self.A or out.get_device() != self.device.index:
+            raise ValueError(f"out must be a contiguous uint8 tensor on {self.device} of >= {self.E}x{self.A} entries")
+        check(lib().mdl_greedy_actions_masked(self._h, ptr(active), ptr(out), self._stream()),
+              "mdl_greedy_actions_masked")
+        return out
+
+    def episode_results(self, out=None):
+        """(total_reward f64 [E], delivered int32 [E], steps int32 [E]) of every env: its fp64
+        ``total_reward``, the number of its packages whose status is delivered and its ``t`` -- what
+        evaluation.py:49-51 reads of a finished episode -- in one small launch, without ``read_state``'s
+        tables.  ``out``: three such tensors of >= E entries on the engine's device; an entry may be
+        None (that output is not written and None is returned in its place)."""
+        if out is None:
+            out = (torch.empty(self.E, dtype=torch.float64, device=self.device),
+                   torch.empty(self.E, dtype=torch.int32, device=self.device),
+                   torch.empty(self.E, dtype=torch.int32, device=self.device))
+        else:
+            if len(out) != 3:
+                raise ValueError("out must be (total_reward, delivered, steps)")
+            for t, dt, name in zip(out, (torch.float64, torch.int32, torch.int32), ("total_reward", "delivered", "steps")):
+                if t is None:      # an output the caller does not want
+                    continue
+                if not isinstance(t, torch.Tensor) or t.dtype != dt:
+                    raise TypeError(f"out {name} must be a {dt} tensor")
+                if not t.is_cuda or t.get_device() != self.device.index or not t.is_contiguous():
+                    raise ValueError(f"out {name} must be contiguous on {self.device}")
+                if t.numel() < self.E:
+                    raise ValueError(f"out {name} holds {t.numel()} entries, needs {self.E}")
+        check(lib().mdl_episode_results(self._h, ptr(out[0]), ptr(out[1]), ptr(out[2]), self._stream()),
+              "mdl_episode_results")
+        return out[0], out[1], out[2]
+
     # ---- checkpoint (SURVEY.md §8(f)4): engine state incl. every env's MT19937 stream ----
     def save_state(self, path=None) -> np.ndarray:
         """Snapshot of the whole engine state as a uint8 array (written to ``path`` as .npy

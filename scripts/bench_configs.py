@@ -16,6 +16,8 @@
                     step against the host-driven loop it replaces
   --qmix-cycle      map-QMIX cycle collection: cycle_begin against reset + build_obs_alt, the joint
                     replay append, and one collector step against the host-driven loop
+  --eval            device-resident evaluation: the greedy agent's mask, episode_results against the
+                    read_state export, and one greedy evaluation against the host-driven loop
 
 Prints one JSON line per config with per-kernel HIP-event times and the
 algorithmic-bytes roofline of SURVEY.md §8(d).
@@ -711,6 +713,161 @@ def run_qmix_cycle(steps):
         ref.close()
 
 
+def run_eval_bench(steps):
+    """Device-resident evaluation ("Evaluation"); the README configuration (map1, A=5,
+    P=100, T=1000, fresh tracker, env e seeded 10 + e) at 100 and 4,096 envs.  hipGraphs of G calls,
+    five interleaved repeats each.
+
+    1. ``greedy_actions()`` against ``greedy_actions_masked`` with an all-ones and with an all-zero
+       mask, 30 steps into the episodes.  get_actions appends this t's spawns to the agent record on
+       every call, so each graph is [greedy_init, G calls]: every replay starts from the same record
+       (the all-zero side carries the same greedy_init).
+    2. ``episode_results`` against the ``mdl_read_state`` export it replaces (all six tables, into
+       preallocated tensors: the allocations ``read_state`` makes are left out).
+    3. One whole greedy evaluation -- reset, greedy_init, T x [actions, step], results, one
+       synchronisation -- by the ``Evaluator`` graph-replayed and eager, against the host-driven loop
+       of tests/test_gpu_greedy.py::run_greedy_episodes; wall time, and wall time / T per step.
+    """
+    import marl_gpu
+    from marl_gpu._lib import check, lib, ptr, stream_handle
+    from marl_gpu.maps import grid_array, load_map, map_path
+    g1 = grid_array(load_map(map_path("map1.txt")))
+    A, P, T, G = 5, 100, 1000, 50
+    dev = torch.device("cuda", 0)
+    reps = max(2, steps // G)
+
+    def wall_ms(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    for E in (100, 4096):
+        seeds = [10 + e for e in range(E)]
+        env = marl_gpu.BatchedEnv(g1, E, A, P, T, seeds=seeds, tracker="fresh")
+        env.reset()
+        env.greedy_init()
+        acts = torch.zeros((E, A), dtype=torch.uint8, device=dev)
+        ones = torch.ones(E, dtype=torch.uint8, device=dev)
+        zeros = torch.zeros(E, dtype=torch.uint8, device=dev)
+        for _ in range(30):
+            env.greedy_actions(out=acts)
+            env.step(acts, auto_reset=False, action_format="codes")
+
+        # 1. the mask's cost
+        def calls(fn):
+            def f():
+                env.greedy_init()
+                for _ in range(G):
+                    fn()
+            return f
+
+        gu = _graph_of(calls(lambda: env.greedy_actions(out=acts)))
+        g1s = _graph_of(calls(lambda: env.greedy_actions_masked(ones, out=acts)))
+        g0s = _graph_of(calls(lambda: env.greedy_actions_masked(zeros, out=acts)))
+        tu, t1, t0 = [], [], []
+        for _ in range(5):
+            tu.append(_replay_us(gu, reps, G))
+            t1.append(_replay_us(g1s, reps, G))
+            t0.append(_replay_us(g0s, reps, G))
+        print(json.dumps({"config": "eval_greedy_mask", "envs": E, "agents": A, "packages": P, "graph_calls": G,
+                          "replays": reps, "greedy_actions_us": tu, "masked_all_ones_us": t1,
+                          "masked_all_zero_us": t0,
+                          "note": "us per call; every graph is [greedy_init, G calls], so each figure carries "
+                                  "1/G of one greedy_init"}), flush=True)
+
+        # 2. the results against the export
+        i32 = dict(dtype=torch.int32, device=dev)
+        res = (torch.zeros(E, dtype=torch.float64, device=dev), torch.zeros(E, **i32), torch.zeros(E, **i32))
+        exp = dict(robots=torch.zeros((E, A, 3), **i32), pkgs=torch.zeros((E, P, 8), **i32), t=torch.zeros(E, **i32),
+                   total=torch.zeros(E, dtype=torch.float64, device=dev), trk=torch.zeros((E, P, 4), **i32),
+                   data=torch.zeros((E, P, 6), **i32))
+
+        def export():
+            check(lib().mdl_read_state(env._h, ptr(exp["robots"]), ptr(exp["pkgs"]), ptr(exp["t"]), ptr(exp["total"]),
+                                       ptr(exp["trk"]), ptr(exp["data"]), stream_handle(dev)), "mdl_read_state")
+
+        def many(fn):
+            def f():
+                for _ in range(G):
+                    fn()
+            return f
+
+        gr, ge = _graph_of(many(lambda: env.episode_results(out=res))), _graph_of(many(export))
+        tr, te = [], []
+        for _ in range(5):
+            tr.append(_replay_us(gr, reps, G))
+            te.append(_replay_us(ge, reps, G))
+        print(json.dumps({"config": "eval_results", "envs": E, "agents": A, "packages": P, "graph_calls": G,
+                          "replays": reps, "episode_results_us": tr, "read_state_export_us": te,
+                          "export_bytes": E * (A * 3 + P * 18 + 1 + 2) * 4, "results_bytes": E * 16}), flush=True)
+        del gu, g1s, g0s, gr, ge
+
+        # 3. one whole greedy evaluation
+        ev = marl_gpu.Evaluator(env)
+        got = {}
+
+        def host_loop():
+            env.reset()
+            env.greedy_init()
+            active = np.arange(E)
+            totals, delivered = np.zeros(E), np.zeros(E, np.int64)
+            while active.size:
+                ids = torch.from_numpy(active.astype(np.int32)).cuda()
+                a = env.greedy_actions(env_ids=ids)
+                _, _, done = env.step(a, env_ids=ids, auto_reset=False, action_format="codes")
+                d = done.cpu().numpy().astype(bool)
+                if d.any():
+                    s = env.read_state()
+                    tot = s["total_reward"].cpu().numpy()
+                    st = s["pkgs"][:, :, 7].cpu().numpy()
+                    for e in active[d]:
+                        totals[e] = tot[e]
+                        delivered[e] = int((st[e] == 3).sum())
+                    active = active[~d]
+            got["host"] = (totals.tolist(), delivered.tolist())
+
+        def evaluator(graph):
+            def f():
+                ev.run("greedy", graph=graph, graph_steps=G)
+                s = ev.summary()
+                got[graph] = (s["rewards"], s["delivered"])
+            return f
+
+        # every run resets the envs (their next layouts): rewound to the built engine before each
+        # run, outside the timed region, all three play the README's episodes
+        built = marl_gpu.BatchedEnv(g1, E, A, P, T, seeds=seeds, tracker="fresh")
+        blob = built.save_state()
+        built.close()
+
+        def rewound(fn):
+            env.load_state(blob)
+            return wall_ms(fn)
+
+        rewound(evaluator(True))                            # eager run + capture
+        rewound(evaluator(True))
+        rewound(host_loop)
+        wg, we, wh = [], [], []
+        for _ in range(5):
+            wg.append(rewound(evaluator(True)))
+            we.append(rewound(evaluator(False)))
+            wh.append(rewound(host_loop))
+        assert got[True] == got[False] == got["host"]
+        print(json.dumps({"config": "eval_greedy_run", "envs": E, "agents": A, "packages": P, "max_time_steps": T,
+                          "graph_steps": G, "evaluator_graph_ms": wg, "evaluator_eager_ms": we, "host_loop_ms": wh,
+                          "evaluator_graph_step_us": [x * 1e3 / T for x in wg],
+                          "evaluator_eager_step_us": [x * 1e3 / T for x in we],
+                          "host_loop_step_us": [x * 1e3 / T for x in wh],
+                          "mean_reward": float(np.mean(got[True][0])),
+                          "launches": {"evaluator": "k_reset, k_greedy_init, T x (k_greedy_act, mdl_step_episode's launches), "
+                                                    "k_episode_results; one copy and one sync at the end",
+                                       "host_loop": "per step: the id list's upload, k_greedy_act, k_step, one D2H "
+                                                    "copy and sync; k_export and two copies whenever an env ends"}}),
+              flush=True)
+        env.close()
+
+
 def run_config1(seconds=5.0):
     """BASELINE.json configs[0]: map1, 5 agents, ONE env, a random agent driving the dict
     API (randomagent.py: np.random.choice over moves and ops per robot) -- plumbing, not a
@@ -749,8 +906,12 @@ def main():
     ap.add_argument("--qmix", action="store_true", help="the QMIX episode-collection measurements only")
     ap.add_argument("--idq", action="store_true", help="the IDQ transition-collection measurements only")
     ap.add_argument("--qmix-cycle", action="store_true", help="the map-QMIX cycle-collection measurements only")
+    ap.add_argument("--eval", action="store_true", help="the device-resident evaluation measurements only")
     a = ap.parse_args()
     torch.cuda.set_device(0)
+    if a.eval:
+        run_eval_bench(a.steps)
+        return
     if a.qmix:
         run_qmix(a.steps)
         return
