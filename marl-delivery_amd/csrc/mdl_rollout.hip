@@ -332,31 +332,39 @@ int rfail(const char* msg, hipError_t e = hipSuccess) {
 
 extern "C" {
 
-int mdl_sample_actions(const float* logits, int64_t n_rows, int32_t n_actions, uint64_t seed, uint64_t offset,
-                       uint8_t* actions, float* log_probs, void* stream) {
-    if (!logits || !actions) return rfail("mdl_sample_actions: null argument");
-    if (n_rows < 0 || n_actions < 1 || n_actions > 256) return rfail("mdl_sample_actions: bad sizes");
+static int sample(const char* what, const float* logits, int64_t n_rows, int32_t n_actions, uint64_t seed,
+                  uint64_t offset, const uint64_t* offset_dev, uint8_t* actions, float* log_probs, void* stream) {
+    char msg[96];
+    if (!logits || !actions) {
+        snprintf(msg, sizeof msg, "%s: null argument", what);
+        return rfail(msg);
+    }
+    if (n_rows < 0 || n_actions < 1 || n_actions > 256) {
+        snprintf(msg, sizeof msg, "%s: bad sizes", what);
+        return rfail(msg);
+    }
     if (n_rows == 0) return 0;
     const int64_t blocks = (n_rows + 255) / 256;
     hipLaunchKernelGGL(mdl::k_sample, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, logits, n_rows,
                        (int)n_actions, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)offset,
-                       (uint32_t)(offset >> 32), (const uint64_t*)nullptr, actions, log_probs);
+                       (uint32_t)(offset >> 32), offset_dev, actions, log_probs);
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : rfail("mdl_sample_actions: launch failed", e);
+    if (e == hipSuccess) return 0;
+    snprintf(msg, sizeof msg, "%s: launch failed", what);
+    return rfail(msg, e);
+}
+
+int mdl_sample_actions(const float* logits, int64_t n_rows, int32_t n_actions, uint64_t seed, uint64_t offset,
+                       uint8_t* actions, float* log_probs, void* stream) {
+    return sample("mdl_sample_actions", logits, n_rows, n_actions, seed, offset, nullptr, actions, log_probs, stream);
 }
 
 int mdl_sample_actions_dev(const float* logits, int64_t n_rows, int32_t n_actions, uint64_t seed,
                            const uint64_t* offset_dev, uint64_t offset_add, uint8_t* actions, float* log_probs,
                            void* stream) {
-    if (!logits || !actions || !offset_dev) return rfail("mdl_sample_actions_dev: null argument");
-    if (n_rows < 0 || n_actions < 1 || n_actions > 256) return rfail("mdl_sample_actions_dev: bad sizes");
-    if (n_rows == 0) return 0;
-    const int64_t blocks = (n_rows + 255) / 256;
-    hipLaunchKernelGGL(mdl::k_sample, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, logits, n_rows,
-                       (int)n_actions, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)offset_add,
-                       (uint32_t)(offset_add >> 32), offset_dev, actions, log_probs);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : rfail("mdl_sample_actions_dev: launch failed", e);
+    if (!offset_dev) return rfail("mdl_sample_actions_dev: null argument");
+    return sample("mdl_sample_actions_dev", logits, n_rows, n_actions, seed, offset_add, offset_dev, actions,
+                  log_probs, stream);
 }
 
 static int select_eps(const char* what, const float* q, const uint8_t* avail, int64_t n_rows, int32_t n_actions,

@@ -149,6 +149,14 @@ class BatchedEnv:
         ends = np.append(brk, self.E)
         self._shape_run_end = np.repeat(ends, np.diff(np.concatenate(([0], ends))))
 
+    def single_map_shape(self, who: str):
+        """(H, W) of the one map shape all envs share; ValueError (``who`` names the caller, whose
+        buffers hold one [H, W]) if the envs mix shapes."""
+        if self._shape_run_end[0] < self.E:
+            raise ValueError(f"{who}: the engine's envs mix map shapes (build one engine per map shape)")
+        H, W = self.grids[int(self.env_map[0])].shape
+        return int(H), int(W)
+
     # ------------------------------------------------------------------ core
     def close(self):
         if getattr(self, "_h", None):

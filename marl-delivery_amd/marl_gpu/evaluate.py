@@ -14,9 +14,9 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from ._capture import Graphed, capture, eval_mode
 from ._lib import check, lib, ptr, stream_handle
-from .qmix_rollout import select_actions_eps
-from .rollout import sample_actions, sample_actions_dev
+from .actions import sample_actions, sample_actions_dev, select_actions_eps
 
 # randomagent.py:16-17 in the engine's action codes (move code | op << 3)
 _RANDOM_MOVES = np.array([3, 4, 1, 2, 0], np.uint8)   # 'U', 'D', 'L', 'R', 'S'
@@ -67,7 +67,7 @@ def random_action_tape(seed: int, n_episodes: int, n_robots: int, max_time_steps
     return np.ascontiguousarray(codes.transpose(1, 0, 2))
 
 
-class Evaluator:
+class Evaluator(Graphed):
     """One evaluation episode per env of ``env`` (a ``BatchedEnv`` whose envs share one map shape;
     build it with tracker="fresh" as the evaluation's agents use -- a stale tracker is cleared before
     the reset).  ``seed`` keys the sampler of a stochastic policy.  Every run resets the envs, which
@@ -86,11 +86,10 @@ class Evaluator:
     does); their actions are never used, the engine does not step them."""
 
     def __init__(self, env, seed: int = 0):
-        if env._shape_run_end[0] < env.E:
-            raise ValueError("Evaluator: the engine's envs mix map shapes (build one engine per map shape)")
+        self._hw = env.single_map_shape("Evaluator")
         self.env = env
         self.seed = int(seed)
-        self.offset = 0
+        self._init_graphs(env.device)
         E, A, dev = env.E, env.A, env.device
         self.active = torch.zeros(E, dtype=torch.uint8, device=dev)
         self.actions = torch.zeros((E, A), dtype=torch.uint8, device=dev)
@@ -99,9 +98,6 @@ class Evaluator:
         self.steps = torch.zeros(E, dtype=torch.int32, device=dev)
         self._log_probs = torch.zeros(E * A, dtype=torch.float32, device=dev)   # the sampler's second output
         self._obs = None              # the policy's observation buffers, used in place
-        self._graphs = None           # (chunk graph, chunk steps, remainder graph or None, remainder steps)
-        self._graph_key = None
-        self._off_dev = torch.zeros(1, dtype=torch.int64, device=dev)   # sampler offset base (uint64 bits)
 
     # ------------------------------------------------------------------ results
     def results(self) -> dict:
@@ -140,7 +136,8 @@ class Evaluator:
         graph=True: the first call runs eagerly, then captures min(L, graph_steps) steps as one
         hipGraph (and the L mod chunk remaining steps as a second one); later calls with the same
         agent object, its parameters at the same addresses, and the same arguments replay them --
-        bit-identical to the eager run.  A tape's graph holds all L steps."""
+        bit-identical to the eager run, in any interleaving (the graph rule, ``_capture``).  A tape's
+        graph holds all L steps."""
         env = self.env
         kind = self._kind(agent)
         L = min(int(max_steps) if max_steps else env.T, env.T)
@@ -155,47 +152,33 @@ class Evaluator:
             if agent.dtype != torch.uint8 or not agent.is_cuda or agent.get_device() != env.device.index \
                     or not agent.is_contiguous():
                 raise TypeError(f"Evaluator: an action tape must be a contiguous uint8 tensor on {env.device}")
-        was_training = kind == "policy" and bool(getattr(agent, "training", False))
-        if kind == "policy" and hasattr(agent, "eval"):
-            agent.eval()
-        try:
+        det = bool(deterministic)
+        with eval_mode(agent):
             if not graph:
                 self._begin(kind)
-                self._steps(kind, agent, 0, L, bool(deterministic), False)
+                self._steps(kind, agent, 0, L, det, False)
                 self._end()
                 return self.results()
             chunk = L if kind == "tape" else min(L, int(graph_steps))
             if chunk < 1:
                 raise ValueError("Evaluator: graph_steps must be >= 1")
-            ptrs = tuple(q.data_ptr() for q in agent.parameters()) if hasattr(agent, "parameters") else ()
-            if kind == "tape":
-                ptrs = (agent.data_ptr(),)
-            key = (kind, ptrs, L, chunk, bool(deterministic))
-            k0 = self._graph_key
             # a graph reads the agent's parameters (or the tape) in place: replay only for the very same object
-            if self._graphs is not None and k0[1] == key and (k0[0] is agent or kind == "greedy"):
-                g, n, g_rem, n_rem = self._graphs
-                self._begin(kind)
-                self._off_dev.fill_(self.offset)
-                for _ in range(L // n):
-                    g.replay()
-                if g_rem is not None:
-                    g_rem.replay()
-                if kind == "policy" and not deterministic:
-                    self.offset += L
+            owners, values = (agent,), (kind, L, chunk, det)
+            g = self._graphs.lookup(owners, values, "chunk")
+            self._begin(kind)
+            if g is not None:
+                g_rem = self._graphs.lookup(owners, values, "rest")
+                graphs = (g,) * (L // chunk) + ((g_rem,) if g_rem is not None else ())
+                self._replay(graphs, L if kind == "policy" and not det else 0)   # only the sampler draws
                 self._end()
                 return self.results()
-            self._begin(kind)                      # this call's episodes, and the warm-up
-            self._steps(kind, agent, 0, L, bool(deterministic), False)
+            self._steps(kind, agent, 0, L, det, False)   # this call's episodes, and the warm-up
             self._end()
-            rem = L % chunk
-            g = self._capture(kind, agent, chunk, bool(deterministic))
-            g_rem = self._capture(kind, agent, rem, bool(deterministic)) if rem else None
-            self._graphs, self._graph_key = (g, chunk, g_rem, rem), (agent, key)
+            for slot, n in (("chunk", chunk), ("rest", L % chunk)):
+                if n:   # n steps as one hipGraph; a tape's graph starts at step 0 (it holds the whole run)
+                    g, _ = capture(env.device, lambda: self._steps(kind, agent, 0, n, det, True))
+                    self._graphs.store(owners, values, slot, g, n)
             return self.results()
-        finally:
-            if was_training and hasattr(agent, "train"):
-                agent.train()
 
     def _begin(self, kind):
         env = self.env
@@ -207,7 +190,7 @@ class Evaluator:
             env.greedy_init()
         elif kind == "policy":
             if self._obs is None:
-                H, W = env.grids[int(env.env_map[0])].shape
+                H, W = self._hw
                 f = dict(dtype=torch.float32, device=env.device)
                 self._obs = dict(actor_map=torch.empty((env.E, env.A, 6, H, W), **f),
                                  actor_vec=torch.empty((env.E, env.A, env.actor_vec_dim), **f))
@@ -242,20 +225,6 @@ class Evaluator:
 
     def _end(self):
         self.env.episode_results(out=(self.rewards, self.delivered, self.steps))
-
-    def _capture(self, kind, agent, n, deterministic):
-        """n steps as one hipGraph.  A tape's graph starts at step 0 (it holds the whole run)."""
-        dev = self.env.device
-        torch.cuda.synchronize(dev)
-        s = torch.cuda.Stream(device=dev)
-        s.wait_stream(torch.cuda.current_stream(dev))
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.stream(s):
-            with torch.cuda.graph(g, stream=s):
-                self._steps(kind, agent, 0, n, deterministic, True)
-        torch.cuda.current_stream(dev).wait_stream(s)
-        torch.cuda.synchronize(dev)
-        return g
 
 
 def run_eval(agent_type: str, env_config: dict, num_episodes: int, policy=None, deterministic: bool | None = None,

@@ -14,88 +14,13 @@ from __future__ import annotations
 
 import torch
 
+from ._capture import Graphed, capture, eval_mode
 from ._lib import check, lib, ptr, stream_handle
-from .qmix_rollout import ACTION_DIM, select_actions_eps, select_actions_eps_dev  # noqa: F401
+from .actions import ACTION_DIM, select_actions_eps, select_actions_eps_dev  # noqa: F401
+from .replay import TransitionReplay
 
 
-class TransitionReplay:
-    """The reference's per-transition ``ReplayBuffer`` (IDQ/networks.py:46-104) as a device ring:
-    observations / next_observations float32 [capacity, *obs_shape], actions int64, rewards
-    float32, dones uint8 [capacity], and the cursor (ptr, size) as an int64 tensor [2] on the
-    device, advanced by ``add`` without a host round trip."""
-
-    def __init__(self, capacity: int, obs_shape, device="cuda"):
-        self.capacity = int(capacity)
-        if self.capacity < 1:
-            raise ValueError("TransitionReplay: capacity must be >= 1")
-        self.obs_shape = (int(obs_shape),) if isinstance(obs_shape, int) else tuple(int(s) for s in obs_shape)
-        self.device = torch.device(device)
-        self.row_floats = 1
-        for s in self.obs_shape:
-            self.row_floats *= s
-        f = dict(dtype=torch.float32, device=self.device)
-        self.observations = torch.zeros((self.capacity,) + self.obs_shape, **f)
-        self.next_observations = torch.zeros((self.capacity,) + self.obs_shape, **f)
-        self.actions = torch.zeros(self.capacity, dtype=torch.int64, device=self.device)
-        self.rewards = torch.zeros(self.capacity, **f)
-        self.dones = torch.zeros(self.capacity, dtype=torch.uint8, device=self.device)
-        self.cursor = torch.zeros(2, dtype=torch.int64, device=self.device)
-        self._rank = None   # int32 [E + 3], mdl_replay_append's scratch
-
-    def add(self, filled, obs, actions, reward, next_obs, done):
-        """One step's ``buffer.add`` calls (IDQ/trainer.py:304-311): for every env with
-        ``filled[e] != 0`` in env order and every agent in order, the row (obs[e, a],
-        actions[e, a], reward[e, a], next_obs[e, a], done[e]).  filled / done uint8 [E], obs /
-        next_obs float32 [E, A, *obs_shape], actions uint8 [E, A], reward float64 [E, A] (stored
-        rounded once to float32), all contiguous on the ring's device.  Two launches, no
-        synchronisation.  A step with more rows than ``capacity`` leaves its last ``capacity``
-        rows, as the sequential adds do."""
-        E, A = actions.shape
-        want = dict(filled=(filled, torch.uint8, E), done=(done, torch.uint8, E), actions=(actions, torch.uint8, E * A),
-                    reward=(reward, torch.float64, E * A), obs=(obs, torch.float32, E * A * self.row_floats),
-                    next_obs=(next_obs, torch.float32, E * A * self.row_floats))
-        for name, (t, dt, n) in want.items():
-            if not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_contiguous() or t.device != self.cursor.device:
-                raise TypeError(f"TransitionReplay.add: {name} must be a contiguous {dt} tensor on {self.cursor.device}")
-            if t.numel() != n:
-                raise ValueError(f"TransitionReplay.add: {name} holds {t.numel()} entries, needs {n}")
-        if self._rank is None or self._rank.numel() < E + 3:
-            self._rank = torch.zeros(E + 3, dtype=torch.int32, device=self.cursor.device)
-        check(lib().mdl_replay_append(ptr(filled), E, A, self.row_floats, ptr(obs), ptr(next_obs), ptr(actions),
-                                      ptr(reward), ptr(done), self.capacity, ptr(self.cursor), ptr(self.observations),
-                                      ptr(self.next_observations), ptr(self.actions), ptr(self.rewards),
-                                      ptr(self.dones), ptr(self._rank), stream_handle(self.cursor.device)),
-              "mdl_replay_append")
-
-    def position(self):
-        """(ptr, size) read from the device: one 16-byte copy and a synchronisation."""
-        p, s = self.cursor.tolist()
-        return int(p), int(s)
-
-    def __len__(self):
-        """The number of stored rows.  Reads the device cursor (``position``): it synchronises."""
-        return self.position()[1]
-
-    def can_sample(self, batch_size: int) -> bool:
-        return len(self) >= int(batch_size)
-
-    def sample(self, batch_size: int, generator=None):
-        """``ReplayBuffer.sample`` (IDQ/networks.py:81-104): ``batch_size`` distinct stored rows as
-        (obs float32, actions int64, rewards float32, next_obs float32, dones float32); with
-        fewer than ``batch_size`` rows stored, all of them in ring order.  Reads the device cursor
-        (one 16-byte copy and a synchronisation): sampling sits on the learner's side of the
-        loop.  The draw is torch's ``randperm`` (``generator``), not numpy's global stream."""
-        size = len(self)
-        if size < int(batch_size):
-            idx = torch.arange(size, device=self.device)
-        else:
-            gdev = generator.device if generator is not None else torch.device("cpu")
-            idx = torch.randperm(size, generator=generator, device=gdev)[:int(batch_size)].to(self.device)
-        return (self.observations[idx], self.actions[idx], self.rewards[idx], self.next_observations[idx],
-                self.dones[idx].float())
-
-
-class IdqCollector:
+class IdqCollector(Graphed):
     """``DQNTrainer.run_episode``'s environment side (IDQ/trainer.py:233-324) on the device.
 
     env: a ``BatchedEnv`` with tracker="fresh", or a stale tracker, which ``begin`` clears before
@@ -121,11 +46,9 @@ class IdqCollector:
         self.env, self.replay = env, replay
         self.seed = int(seed)
         self.ops_are_ints = bool(ops_are_ints)
-        self.offset = 0
+        self._init_graphs(env.device)
         E, A = env.E, env.A
-        if env._shape_run_end[0] < E:
-            raise ValueError("IdqCollector: the engine's envs mix map shapes (build one engine per map shape)")
-        H, W = env.grids[int(env.env_map[0])].shape
+        H, W = env.single_map_shape("IdqCollector")
         if replay.obs_shape != (6, H, W) or replay.cursor.device != env.device:
             raise ValueError(f"IdqCollector: replay must hold (6, {H}, {W}) observations on {env.device}")
         dev = env.device
@@ -141,9 +64,6 @@ class IdqCollector:
         self.filled = torch.zeros(E, **b)
         self.active = torch.zeros(E, **b)
         self.episode_return = torch.zeros(E, dtype=torch.float64, device=dev)
-        self._graph = None            # hipGraph of one whole collect (collect(graph=True))
-        self._graph_key = None        # (agent, parameter addresses, steps) the graph was captured with
-        self._off_dev = torch.zeros(1, dtype=torch.int64, device=dev)   # selection offset base (uint64 bits)
         self._eps_dev = torch.zeros(1, dtype=torch.float32, device=dev)
 
     def begin(self):
@@ -191,45 +111,25 @@ class IdqCollector:
 
         graph=True: the first call runs eagerly and captures the whole collect as one hipGraph;
         later calls with the same agent (the very same module, its parameters still at the
-        captured addresses) and step count replay it -- bit-identical to eager calls (epsilon
-        and the selection's offset base live on the device, as the replay cursor does)."""
+        captured addresses) and step count replay it -- bit-identical to eager calls, in any
+        interleaving (the graph rule, ``_capture``; epsilon lives on the device, as the replay
+        cursor does)."""
         n = self.env.T if max_steps is None else min(int(max_steps), self.env.T)
-        was_training = bool(getattr(agent, "training", False))
-        if hasattr(agent, "eval"):
-            agent.eval()
-        try:
+        with eval_mode(agent):
             if not graph:
                 return self._run(agent, float(epsilon), False, n)
-            ptrs = tuple(q.data_ptr() for q in agent.parameters()) if hasattr(agent, "parameters") else ()
-            k0 = self._graph_key
-            if self._graph is not None and k0[0] is agent and k0[1] == ptrs and k0[2] == n:
+            g = self._graphs.lookup((agent,), (n,))
+            if g is not None:
                 self._eps_dev.fill_(float(epsilon))
-                self._graph.replay()
-                self.offset += n
+                self._replay((g,), n)
                 self.cur = n & 1
                 return self.episode_return
             out = self._run(agent, float(epsilon), False, n)   # this call's episodes, and the warm-up
-            self._capture(agent, (agent, ptrs, n), n)
+            off0, cur0 = self.offset, self.cur
+            g, _ = capture(self.env.device, lambda: self._run(agent, 0.0, True, n))
+            self.offset, self.cur = off0, cur0   # capture ran nothing
+            self._graphs.store((agent,), (n,), None, g, n)
             return out
-        finally:
-            if was_training and hasattr(agent, "train"):
-                agent.train()
-
-    def _capture(self, agent, key, n):
-        dev = self.env.device
-        torch.cuda.synchronize(dev)
-        self._off_dev.fill_(self.offset)
-        s = torch.cuda.Stream(device=dev)
-        s.wait_stream(torch.cuda.current_stream(dev))
-        g = torch.cuda.CUDAGraph()
-        off0, cur0 = self.offset, self.cur
-        with torch.cuda.stream(s):
-            with torch.cuda.graph(g, stream=s):
-                self._run(agent, 0.0, True, n)
-        torch.cuda.current_stream(dev).wait_stream(s)
-        torch.cuda.synchronize(dev)
-        self.offset, self.cur = off0, cur0   # capture ran nothing
-        self._graph, self._graph_key = g, key
 
     def _run(self, agent, epsilon, dev_args, n):
         env = self.env

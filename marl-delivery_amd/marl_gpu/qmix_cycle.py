@@ -16,140 +16,12 @@ from __future__ import annotations
 
 import torch
 
-from ._lib import check, lib, ptr, stream_handle
-from .qmix_rollout import _q_avail
+from ._capture import Graphed, capture, eval_mode
+from .actions import select_actions_eps_mark, select_actions_eps_mark_dev
+from .replay import JointReplay
 
 
-def select_actions_eps_mark(q: torch.Tensor, epsilon: float, seed: int, offset: int, avail=None, out=None,
-                            explored=None):
-    """``select_actions_eps`` (the same actions, bit for bit) that also reports which rows explored:
-    returns (actions uint8 [N], explored uint8 [N]); explored is 1 where the row's uniform fell
-    below epsilon and the row had an available action."""
-    q, avail = _q_avail(q, avail)
-    N, n_act = q.shape
-    if out is None:
-        out = torch.empty(N, dtype=torch.uint8, device=q.device)
-    if explored is None:
-        explored = torch.empty(N, dtype=torch.uint8, device=q.device)
-    check(lib().mdl_select_actions_eps_mark(ptr(q), ptr(avail), N, n_act, float(epsilon), seed & (2**64 - 1),
-                                            offset & (2**64 - 1), ptr(out), ptr(explored),
-                                            stream_handle(q.device)), "mdl_select_actions_eps_mark")
-    return out, explored
-
-
-def select_actions_eps_mark_dev(q: torch.Tensor, epsilon_dev: torch.Tensor, seed: int, offset_dev: torch.Tensor,
-                                offset_add: int, avail=None, out=None, explored=None):
-    """``select_actions_eps_mark`` with epsilon (float32 tensor [1]) and the offset base (uint64 bits
-    in an int64 tensor [1]) read on the device, so the launch can live in a replayed hipGraph."""
-    q, avail = _q_avail(q, avail)
-    N, n_act = q.shape
-    if epsilon_dev.dtype != torch.float32 or offset_dev.dtype != torch.int64:
-        raise TypeError("epsilon_dev must be float32 and offset_dev int64 (uint64 bits)")
-    if out is None:
-        out = torch.empty(N, dtype=torch.uint8, device=q.device)
-    if explored is None:
-        explored = torch.empty(N, dtype=torch.uint8, device=q.device)
-    check(lib().mdl_select_actions_eps_mark_dev(ptr(q), ptr(avail), N, n_act, ptr(epsilon_dev), seed & (2**64 - 1),
-                                                ptr(offset_dev), offset_add & (2**64 - 1), ptr(out), ptr(explored),
-                                                stream_handle(q.device)), "mdl_select_actions_eps_mark_dev")
-    return out, explored
-
-
-def _shape(s):
-    return (int(s),) if isinstance(s, int) else tuple(int(x) for x in s)
-
-
-class JointReplay:
-    """The ``qmix/`` trainer's joint ``ReplayBuffer`` (qmix/networks.py:155-239) as a device ring,
-    its tensors named and shaped as the reference's arrays: states / next_states float32
-    [capacity, *state_shape], observations / next_observations float32 [capacity, A, *obs_shape],
-    actions int64 [capacity, A], total_reward float32 [capacity, 1], dones uint8 [capacity, 1], and
-    the cursor (ptr, size) as an int64 tensor [2] on the device, advanced by ``add`` without a host
-    round trip."""
-
-    def __init__(self, capacity: int, n_agents: int, obs_shape, state_shape, device="cuda"):
-        self.capacity = int(capacity)
-        if self.capacity < 1:
-            raise ValueError("JointReplay: capacity must be >= 1")
-        self.n_agents = int(n_agents)
-        if self.n_agents < 1:
-            raise ValueError("JointReplay: n_agents must be >= 1")
-        self.obs_shape, self.state_shape = _shape(obs_shape), _shape(state_shape)
-        self.device = torch.device(device)
-        self.obs_floats = self.state_floats = 1
-        for s in self.obs_shape:
-            self.obs_floats *= s
-        for s in self.state_shape:
-            self.state_floats *= s
-        f = dict(dtype=torch.float32, device=self.device)
-        cap, A = self.capacity, self.n_agents
-        self.states = torch.zeros((cap,) + self.state_shape, **f)
-        self.next_states = torch.zeros((cap,) + self.state_shape, **f)
-        self.observations = torch.zeros((cap, A) + self.obs_shape, **f)
-        self.next_observations = torch.zeros((cap, A) + self.obs_shape, **f)
-        self.actions = torch.zeros((cap, A), dtype=torch.int64, device=self.device)
-        self.total_reward = torch.zeros((cap, 1), **f)
-        self.dones = torch.zeros((cap, 1), dtype=torch.uint8, device=self.device)
-        self.cursor = torch.zeros(2, dtype=torch.int64, device=self.device)
-
-    def add(self, state, next_state, obs, next_obs, actions, reward, done):
-        """One step's ``buffer.add`` calls (qmix/trainer.py:380-388), one joint row per env in env
-        order: state / next_state float32 [E, *state_shape], obs / next_obs float32
-        [E, A, *obs_shape], actions uint8 [E, A], reward float64 [E] (stored rounded once to
-        float32), done uint8 [E], all contiguous on the ring's device.  Two launches, no
-        synchronisation.  A step with more envs than ``capacity`` leaves its last ``capacity`` rows,
-        as the sequential adds do."""
-        E, A = actions.shape
-        if A != self.n_agents:
-            raise ValueError(f"JointReplay.add: actions has {A} agents, the ring {self.n_agents}")
-        want = dict(state=(state, torch.float32, E * self.state_floats),
-                    next_state=(next_state, torch.float32, E * self.state_floats),
-                    obs=(obs, torch.float32, E * A * self.obs_floats),
-                    next_obs=(next_obs, torch.float32, E * A * self.obs_floats),
-                    actions=(actions, torch.uint8, E * A), reward=(reward, torch.float64, E),
-                    done=(done, torch.uint8, E))
-        for name, (t, dt, n) in want.items():
-            if not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_contiguous() or t.device != self.cursor.device:
-                raise TypeError(f"JointReplay.add: {name} must be a contiguous {dt} tensor on {self.cursor.device}")
-            if t.numel() != n:
-                raise ValueError(f"JointReplay.add: {name} holds {t.numel()} entries, needs {n}")
-        check(lib().mdl_replay_append_joint(E, A, self.state_floats, self.obs_floats, ptr(state), ptr(next_state),
-                                            ptr(obs), ptr(next_obs), ptr(actions), ptr(reward), ptr(done),
-                                            self.capacity, ptr(self.cursor), ptr(self.states), ptr(self.next_states),
-                                            ptr(self.observations), ptr(self.next_observations), ptr(self.actions),
-                                            ptr(self.total_reward), ptr(self.dones),
-                                            stream_handle(self.cursor.device)), "mdl_replay_append_joint")
-
-    def position(self):
-        """(ptr, size) read from the device: one 16-byte copy and a synchronisation."""
-        p, s = self.cursor.tolist()
-        return int(p), int(s)
-
-    def __len__(self):
-        """The number of stored rows.  Reads the device cursor (``position``): it synchronises."""
-        return self.position()[1]
-
-    def can_sample(self, batch_size: int) -> bool:
-        return len(self) >= int(batch_size)
-
-    def sample(self, batch_size: int, generator=None):
-        """``ReplayBuffer.sample`` (qmix/networks.py:200-235): ``batch_size`` distinct stored rows as
-        the reference's tuple in the reference's order, (states, next_states, obs, next_obs,
-        actions int64, total_rewards float32 [B, 1], dones float32 [B, 1]); with fewer than
-        ``batch_size`` rows stored, all of them in ring order; an empty ring gives empty tensors.
-        Reads the device cursor (a synchronisation): sampling sits on the learner's side of the
-        loop.  The draw is torch's ``randperm`` (``generator``), not numpy's global stream."""
-        size = len(self)
-        if size < int(batch_size):
-            idx = torch.arange(size, device=self.device)
-        else:
-            gdev = generator.device if generator is not None else torch.device("cpu")
-            idx = torch.randperm(size, generator=generator, device=gdev)[:int(batch_size)].to(self.device)
-        return (self.states[idx], self.next_states[idx], self.observations[idx], self.next_observations[idx],
-                self.actions[idx], self.total_reward[idx], self.dones[idx].float())
-
-
-class QmixCycleCollector:
+class QmixCycleCollector(Graphed):
     """``QMixTrainer.collect_and_train_cycle``'s environment side (qmix/trainer.py:324-403) on the
     device.
 
@@ -172,11 +44,9 @@ class QmixCycleCollector:
     def __init__(self, env, replay: JointReplay, seed: int = 0, hidden_dim: int | None = None):
         self.env, self.replay = env, replay
         self.seed = int(seed)
-        self.offset = 0
+        self._init_graphs(env.device)
         E, A = env.E, env.A
-        if env._shape_run_end[0] < E:
-            raise ValueError("QmixCycleCollector: the engine's envs mix map shapes (build one engine per map shape)")
-        H, W = env.grids[int(env.env_map[0])].shape
+        H, W = env.single_map_shape("QmixCycleCollector")
         ss = replay.state_shape
         if replay.obs_shape != (6, H, W) or len(ss) != 3 or ss[0] != 7 or replay.n_agents != A \
                 or replay.cursor.device != env.device:
@@ -201,9 +71,6 @@ class QmixCycleCollector:
         self.completed_steps = torch.zeros(E, dtype=torch.int32, device=dev)
         self.cycle_completed = None          # [n_steps, E] uint8, written by cycle
         self.cycle_completed_return = None   # [n_steps, E] float64
-        self._graphs = {}             # starting slot -> hipGraph of one whole cycle (cycle(graph=True))
-        self._graph_key = None        # (agent, parameter addresses, steps) the graphs were captured with
-        self._off_dev = torch.zeros(1, dtype=torch.int64, device=dev)   # selection offset base (uint64 bits)
         self._eps_dev = torch.zeros(1, dtype=torch.float32, device=dev)
 
     def begin(self):
@@ -269,9 +136,9 @@ class QmixCycleCollector:
 
         graph=True: the first call runs eagerly and captures the whole cycle as one hipGraph; later
         calls with the same agent (the very same module, its parameters still at the captured
-        addresses) and step count replay it -- bit-identical to eager calls (epsilon and the
-        selection's offset base live on the device, as the replay cursor does).  A cycle of an odd
-        number of steps ends on the other observation slot, which has a graph of its own."""
+        addresses) and step count replay it -- bit-identical to eager calls, in any interleaving (the
+        graph rule, ``_capture``; epsilon lives on the device, as the replay cursor does).  A cycle
+        of an odd number of steps ends on the other observation slot, which has a graph of its own."""
         n = int(n_steps)
         if n < 1:
             raise ValueError("cycle: n_steps must be >= 1")
@@ -279,48 +146,28 @@ class QmixCycleCollector:
         if self.cycle_completed is None or self.cycle_completed.shape[0] != n:
             self.cycle_completed = torch.zeros((n, self.env.E), dtype=torch.uint8, device=dev)
             self.cycle_completed_return = torch.zeros((n, self.env.E), dtype=torch.float64, device=dev)
-            self._graphs, self._graph_key = {}, None
-        was_training = bool(getattr(agent, "training", False))
-        if hasattr(agent, "eval"):
-            agent.eval()
-        try:
+            self._graphs.clear()      # they write the old buffers
+        with eval_mode(agent):
             if not graph:
                 self._run(agent, float(epsilon), False, n)
                 return self.cycle_completed, self.cycle_completed_return
-            ptrs = tuple(q.data_ptr() for q in agent.parameters()) if hasattr(agent, "parameters") else ()
-            k0 = self._graph_key
-            if k0 is None or k0[0] is not agent or k0[1] != ptrs or k0[2] != n:
-                self._graphs, self._graph_key = {}, (agent, ptrs, n)
+            if not self._graphs.matches((agent,), (n,)):
                 self._run(agent, float(epsilon), False, n)   # this call's steps, and the warm-up
                 self._capture(agent, n)
                 return self.cycle_completed, self.cycle_completed_return
-            if self.cur not in self._graphs:
-                self._capture(agent, n)
+            g = self._graphs.lookup((agent,), (n,), self.cur) or self._capture(agent, n)
             self._eps_dev.fill_(float(epsilon))
-            self._off_dev.fill_(self.offset)
-            self._graphs[self.cur].replay()
-            self.offset += n
+            self._replay((g,), n)
             self.cur = (self.cur + n) & 1
             return self.cycle_completed, self.cycle_completed_return
-        finally:
-            if was_training and hasattr(agent, "train"):
-                agent.train()
 
     def _capture(self, agent, n):
         """Capture n steps that start on the current slot (the capture itself runs nothing)."""
-        dev = self.env.device
-        torch.cuda.synchronize(dev)
-        s = torch.cuda.Stream(device=dev)
-        s.wait_stream(torch.cuda.current_stream(dev))
-        g = torch.cuda.CUDAGraph()
         off0, cur0 = self.offset, self.cur
-        with torch.cuda.stream(s):
-            with torch.cuda.graph(g, stream=s):
-                self._run(agent, 0.0, True, n)
-        torch.cuda.current_stream(dev).wait_stream(s)
-        torch.cuda.synchronize(dev)
+        g, _ = capture(self.env.device, lambda: self._run(agent, 0.0, True, n))
         self.offset, self.cur = off0, cur0
-        self._graphs[cur0] = g
+        self._graphs.store((agent,), (n,), cur0, g, n)
+        return g
 
     def _run(self, agent, epsilon, dev_args, n):
         for k in range(n):

@@ -15,61 +15,13 @@ from __future__ import annotations
 
 import torch
 
+from ._capture import Graphed, capture, eval_mode
 from ._lib import check, lib, ptr, stream_handle
-
-ACTION_DIM = 15  # QMIX/trainer.py: num_move_actions * num_pkg_ops
-
-
-def _q_avail(q, avail):
-    if q.dtype != torch.float32 or not q.is_contiguous():
-        q = q.float().contiguous()
-    if q.dim() != 2:
-        raise ValueError("q must be [rows, n_actions]")
-    if avail is not None:
-        if avail.shape != q.shape:
-            raise ValueError("avail must have q's shape")
-        if avail.dtype != torch.uint8 or not avail.is_contiguous():
-            avail = avail.to(torch.uint8).contiguous()
-    return q, avail
+from .actions import ACTION_DIM, select_actions_eps, select_actions_eps_dev  # noqa: F401
+from .replay import EpisodeReplay  # noqa: F401
 
 
-def select_actions_eps(q: torch.Tensor, epsilon: float, seed: int, offset: int, avail=None, out=None):
-    """Epsilon-greedy selection over Q-values (QMIX/trainer.py:298-319).
-
-    q: float32 [N, n_actions] on the device; avail: bool/uint8 of the same shape or None
-    (= every action available).  Returns actions uint8 [N].  A row explores with
-    probability epsilon and then takes a uniformly drawn available action; otherwise it
-    takes the first available action with the largest q.  The draw is the library's own
-    Philox4x32-10 stream keyed by (seed, offset, row) -- include/mdl_engine.h states it
-    exactly --: deterministic, independent of launch shape."""
-    q, avail = _q_avail(q, avail)
-    N, n_act = q.shape
-    if out is None:
-        out = torch.empty(N, dtype=torch.uint8, device=q.device)
-    check(lib().mdl_select_actions_eps(ptr(q), ptr(avail), N, n_act, float(epsilon), seed & (2**64 - 1),
-                                       offset & (2**64 - 1), ptr(out), stream_handle(q.device)),
-          "mdl_select_actions_eps")
-    return out
-
-
-def select_actions_eps_dev(q: torch.Tensor, epsilon_dev: torch.Tensor, seed: int, offset_dev: torch.Tensor,
-                           offset_add: int, avail=None, out=None):
-    """``select_actions_eps`` with epsilon (float32 tensor [1]) and the offset base (uint64
-    bits in an int64 tensor [1]; the offset is ``offset_dev[0] + offset_add``) read on the
-    device, so the launch can live in a replayed hipGraph."""
-    q, avail = _q_avail(q, avail)
-    N, n_act = q.shape
-    if epsilon_dev.dtype != torch.float32 or offset_dev.dtype != torch.int64:
-        raise TypeError("epsilon_dev must be float32 and offset_dev int64 (uint64 bits)")
-    if out is None:
-        out = torch.empty(N, dtype=torch.uint8, device=q.device)
-    check(lib().mdl_select_actions_eps_dev(ptr(q), ptr(avail), N, n_act, ptr(epsilon_dev), seed & (2**64 - 1),
-                                           ptr(offset_dev), offset_add & (2**64 - 1), ptr(out),
-                                           stream_handle(q.device)), "mdl_select_actions_eps_dev")
-    return out
-
-
-class QmixCollector:
+class QmixCollector(Graphed):
     """``collect_data_iteration`` (QMIX/trainer.py:333-528) on the device: one episode per env.
 
     env: a ``BatchedEnv`` built like the trainer's (shaping="qmix"; tracker="fresh", or a
@@ -97,11 +49,9 @@ class QmixCollector:
         if L < 1:
             raise ValueError("QmixCollector: episode_limit must be >= 1")
         self.seed = int(seed)
-        self.offset = 0
+        self._init_graphs(env.device)
         E, A = env.E, env.A
-        if env._shape_run_end[0] < E:
-            raise ValueError("QmixCollector: the engine's envs mix map shapes (build one engine per map shape)")
-        H, W = env.grids[int(env.env_map[0])].shape
+        H, W = env.single_map_shape("QmixCollector")
         dev = env.device
         f = dict(dtype=torch.float32, device=dev)
         b = dict(dtype=torch.uint8, device=dev)
@@ -119,9 +69,6 @@ class QmixCollector:
         self.hidden = None            # [E*A, Hd], allocated by the first collect
         self.episode_return = torch.zeros(E, dtype=torch.float64, device=dev)
         self.episode_length = torch.zeros(E, dtype=torch.int64, device=dev)
-        self._graph = None            # hipGraph of one whole collect (collect(graph=True))
-        self._graph_key = None        # (agent, parameter addresses) the graph was captured with
-        self._off_dev = torch.zeros(1, dtype=torch.int64, device=dev)   # selection offset base (uint64 bits)
         self._eps_dev = torch.zeros(1, **f)
 
     def _slot(self, k):
@@ -143,46 +90,23 @@ class QmixCollector:
 
         graph=True: the first call runs eagerly and captures the whole collect (reset,
         forwards, selection, steps, observations) as one hipGraph; later calls with the same
-        agent replay it -- bit-identical to eager calls (epsilon and the selection's offset
-        base live on the device).  The returned tensors are the graph's static buffers:
-        consume them (``EpisodeReplay.add``) before the next collect."""
-        was_training = bool(getattr(agent, "training", False))
-        if hasattr(agent, "eval"):
-            agent.eval()
-        try:
+        agent replay it -- bit-identical to eager calls, in any interleaving (the graph rule,
+        ``_capture``; epsilon lives on the device).  The returned tensors are the graph's static
+        buffers: consume them (``EpisodeReplay.add``) before the next collect."""
+        with eval_mode(agent):
             if not graph:
                 return self._run(agent, float(epsilon), False)
-            # the graph reads the module's parameters in place: replay only for the very same module
-            # whose parameters still live at the captured addresses (MappoRollout.collect's rule)
-            ptrs = tuple(q.data_ptr() for q in agent.parameters()) if hasattr(agent, "parameters") else ()
-            k0 = self._graph_key
-            if self._graph is not None and k0[0] is agent and k0[1] == ptrs:
+            g = self._graphs.lookup((agent,), ())
+            if g is not None:
                 self._eps_dev.fill_(float(epsilon))
-                self._graph.replay()
-                self.offset += self.L
+                self._replay((g,), self.L)
                 return self.batch()
             out = self._run(agent, float(epsilon), False)   # this call's episodes, and the warm-up
-            self._capture(agent, (agent, ptrs))
+            off0 = self.offset
+            g, _ = capture(self.env.device, lambda: self._run(agent, 0.0, True))
+            self.offset = off0   # capture ran nothing
+            self._graphs.store((agent,), (), None, g, self.L)
             return out
-        finally:
-            if was_training and hasattr(agent, "train"):
-                agent.train()
-
-    def _capture(self, agent, key):
-        dev = self.env.device
-        torch.cuda.synchronize(dev)
-        self._off_dev.fill_(self.offset)
-        s = torch.cuda.Stream(device=dev)
-        s.wait_stream(torch.cuda.current_stream(dev))
-        g = torch.cuda.CUDAGraph()
-        off0 = self.offset
-        with torch.cuda.stream(s):
-            with torch.cuda.graph(g, stream=s):
-                self._run(agent, 0.0, True)
-        torch.cuda.current_stream(dev).wait_stream(s)
-        torch.cuda.synchronize(dev)
-        self.offset = off0   # capture ran nothing
-        self._graph, self._graph_key = g, key
 
     def _run(self, agent, epsilon: float, dev_args: bool):
         env, L = self.env, self.L
@@ -215,74 +139,3 @@ class QmixCollector:
                                    stream_handle(env.device)), "mdl_read_state")
         torch.sum(self.filled, dim=0, dtype=torch.int64, out=self.episode_length)
         return self.batch()
-
-
-class EpisodeReplay:
-    """The reference's episode ``ReplayBuffer`` (QMIX/networks.py:209-318) as a time-major ring
-    of ``capacity`` episodes in plain torch ops, on the device of the template's tensors.
-
-    ``collector``: a ``QmixCollector`` or one of its batches (a dict with so, vo, gs, gv, u, r,
-    terminated, filled) -- the template for shapes, dtypes and device.
-
-    ``add`` stores a batch's E episodes in env order; the reference stores each episode when it
-    terminates, i.e. in termination order.  Only the eviction order inside one batch differs.
-    """
-
-    FIELDS = ("so", "vo", "gs", "gv", "u", "r", "terminated", "filled")
-
-    def __init__(self, capacity: int, collector, n_actions: int = ACTION_DIM):
-        self.capacity = int(capacity)
-        if self.capacity < 1:
-            raise ValueError("EpisodeReplay: capacity must be >= 1")
-        self.n_actions = int(n_actions)
-        tpl = collector if isinstance(collector, dict) else collector.batch()
-        self.buf = {}
-        for k in self.FIELDS:
-            t = tpl[k]
-            self.buf[k] = torch.zeros((t.shape[0], self.capacity) + tuple(t.shape[2:]), dtype=t.dtype, device=t.device)
-        self.L = tpl["u"].shape[0]
-        self.device = tpl["u"].device
-        self.size = 0
-        self.idx = 0
-
-    def __len__(self):
-        return self.size
-
-    def add(self, batch):
-        """Store the E episodes of ``batch`` (env order) in the next E ring slots, evicting the
-        oldest episodes once the ring is full."""
-        E = batch["u"].shape[1]
-        first = max(0, E - self.capacity)   # a batch larger than the ring keeps its last `capacity` episodes
-        slots = (torch.arange(first, E) + self.idx) % self.capacity
-        slots = slots.to(self.device)
-        for k in self.FIELDS:
-            self.buf[k][:, slots] = batch[k][:, first:]
-        self.idx = (self.idx + E) % self.capacity
-        self.size = min(self.capacity, self.size + E)
-
-    def sample(self, batch_size: int, generator=None):
-        """``batch_size`` distinct stored episodes as the reference's dictionary
-        (QMIX/networks.py:299-314), episode-major: so / vo / gs / gv and their ``_next`` forms
-        ([B, L, ...]; ``*_next`` is the same gathered tensor shifted by one slot, not a second
-        copy), u int64 [B, L, A, 1], r [B, L, 1], avail_u / avail_u_next (all ones, [B, L, A,
-        n_actions]), terminated and padded (= 1 - filled) float32 [B, L, 1]."""
-        B = int(batch_size)
-        if B < 1 or self.size < B:
-            raise ValueError(f"EpisodeReplay holds {self.size} episodes, cannot sample {B}")
-        gdev = generator.device if generator is not None else torch.device("cpu")
-        idx = torch.randperm(self.size, generator=generator, device=gdev)[:B].to(self.device)
-        L = self.L
-        out = {}
-        for k in ("so", "vo", "gs", "gv"):
-            x = self.buf[k][:, idx].transpose(0, 1)   # [B, L+1, ...]
-            out[k] = x[:, :L]
-            out[k + "_next"] = x[:, 1:]
-        A = self.buf["u"].shape[2]
-        out["u"] = self.buf["u"][:, idx].transpose(0, 1).long().unsqueeze(-1)
-        out["r"] = self.buf["r"][:, idx].transpose(0, 1).unsqueeze(-1)
-        ones = torch.ones((), dtype=torch.float32, device=self.device).expand(B, L, A, self.n_actions)
-        out["avail_u"] = ones
-        out["avail_u_next"] = ones
-        out["terminated"] = self.buf["terminated"][:, idx].transpose(0, 1).float().unsqueeze(-1)
-        out["padded"] = 1.0 - self.buf["filled"][:, idx].transpose(0, 1).float().unsqueeze(-1)
-        return out

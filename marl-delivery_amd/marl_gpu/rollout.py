@@ -12,42 +12,9 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from ._capture import Graphed, capture
 from ._lib import check, lib, ptr, stream_handle
-
-ACTION_DIM = 15  # MAPPO/trainer.py:41
-
-
-def sample_actions(logits: torch.Tensor, seed: int, offset: int, out=None):
-    """``Categorical(logits=logits).sample()`` and ``.log_prob`` (MAPPO/trainer.py:141-143).
-
-    logits: float32 [N, n_actions] on the device.  Returns (actions uint8 [N],
-    log_probs float32 [N]).  The draw is the library's own Philox4x32-10 stream
-    keyed by (seed, offset, row): deterministic, independent of launch shape.
-    """
-    if logits.dtype != torch.float32 or not logits.is_contiguous():
-        logits = logits.float().contiguous()
-    N, n_act = logits.shape
-    if out is None:
-        acts = torch.empty(N, dtype=torch.uint8, device=logits.device)
-        lp = torch.empty(N, dtype=torch.float32, device=logits.device)
-    else:
-        acts, lp = out
-    check(lib().mdl_sample_actions(ptr(logits), N, n_act, seed & (2**64 - 1), offset & (2**64 - 1), ptr(acts),
-                                   ptr(lp), stream_handle(logits.device)), "mdl_sample_actions")
-    return acts, lp
-
-
-def sample_actions_dev(logits: torch.Tensor, seed: int, offset_dev: torch.Tensor, offset_add: int, out):
-    """``sample_actions`` at offset ``offset_dev[0] + offset_add`` with the base read on the
-    device (uint64 tensor [1]), so the launch can live in a replayed hipGraph."""
-    if logits.dtype != torch.float32 or not logits.is_contiguous():
-        logits = logits.float().contiguous()
-    N, n_act = logits.shape
-    acts, lp = out
-    check(lib().mdl_sample_actions_dev(ptr(logits), N, n_act, seed & (2**64 - 1), ptr(offset_dev),
-                                       offset_add & (2**64 - 1), ptr(acts), ptr(lp), stream_handle(logits.device)),
-          "mdl_sample_actions_dev")
-    return acts, lp
+from .actions import ACTION_DIM, sample_actions, sample_actions_dev  # noqa: F401
 
 
 def gae(rewards, values, next_value, dones, gamma=0.99, gae_lambda=0.95, out=None):
@@ -75,7 +42,7 @@ def gae(rewards, values, next_value, dones, gamma=0.99, gae_lambda=0.95, out=Non
     return adv, ret
 
 
-class MappoRollout:
+class MappoRollout(Graphed):
     """``collect_rollouts`` (MAPPO/trainer.py:154-290) on the device.
 
     env: a ``BatchedEnv`` built like the trainer's (tracker="mappo", shaping="mappo",
@@ -88,12 +55,10 @@ class MappoRollout:
         self.env = env
         self.T = int(rollout_steps)
         self.seed = int(seed)
-        self.offset = 0
+        self._init_graphs(env.device)
         self.gamma, self.gae_lambda = gamma, gae_lambda
         E, A = env.E, env.A
-        if env._shape_run_end[0] < E:   # the buffers hold one [H, W]; a mixed-shape batch needs one rollout per group
-            raise ValueError("MappoRollout: the engine's envs mix map shapes (build one engine per map shape)")
-        H, W = env.grids[int(env.env_map[0])].shape
+        H, W = env.single_map_shape("MappoRollout")
         dev = env.device
         f = dict(dtype=torch.float32, device=dev)
         T = self.T
@@ -108,10 +73,7 @@ class MappoRollout:
         self.mb_values = torch.zeros((T, E), **f)
         self.next_obs = env.obs_buffers(E, H, W)
         self._r_env = torch.zeros(E, dtype=torch.float64, device=dev)
-        self._graph = None          # hipGraph of one whole rollout (collect(graph=True))
-        self._graph_key = None      # (actor, critic, parameter addresses) the graph was captured with
         self._graph_out = None
-        self._off_dev = torch.zeros(1, dtype=torch.int64, device=dev)   # sampler offset base (uint64 bits)
 
     def _slot(self, k):
         return dict(actor_map=self.mb_obs[k], actor_vec=self.mb_vector_obs[k], critic_map=self.mb_global_states[k],
@@ -122,40 +84,21 @@ class MappoRollout:
         """One rollout of ``rollout_steps`` env steps.  graph=True: the first call runs
         eagerly and captures the whole rollout (policy forwards, sampling, steps,
         observations, GAE) as one hipGraph; later calls with the same actor/critic replay
-        it -- bit-identical to eager calls (the sampler's offset base lives on the
-        device and advances inside the graph).  The returned tensors are the graph's
-        static buffers: consume them before the next collect."""
+        it -- bit-identical to eager calls, in any interleaving (the graph rule, ``_capture``).
+        The returned tensors are the graph's static buffers: consume them before the next
+        collect."""
         if not graph:
             return self._run(actor, critic, False)
-        # the graph reads the modules' parameters in place: replay only for the very same modules
-        # (strong references, compared by identity) whose parameters still live at the captured
-        # addresses (load_state_dict copies in place; rebinding ``param.data`` does not)
-        ptrs = tuple(q.data_ptr() for m in (actor, critic) if hasattr(m, "parameters") for q in m.parameters())
-        key = (actor, critic, ptrs)
-        k0 = self._graph_key
-        if self._graph is not None and k0[0] is actor and k0[1] is critic and k0[2] == ptrs:
-            self._graph.replay()
-            self.offset += self.T
+        g = self._graphs.lookup((actor, critic), ())
+        if g is not None:
+            self._replay((g,), self.T)
             return self._graph_out
         out = self._run(actor, critic, False)        # this call's rollout, and the warm-up
-        self._capture(actor, critic, key)
-        return out
-
-    def _capture(self, actor, critic, key):
-        dev = self.env.device
-        torch.cuda.synchronize(dev)
-        self._off_dev.fill_(self.offset)
-        s = torch.cuda.Stream(device=dev)
-        s.wait_stream(torch.cuda.current_stream(dev))
-        g = torch.cuda.CUDAGraph()
         off0 = self.offset
-        with torch.cuda.stream(s):
-            with torch.cuda.graph(g, stream=s):
-                self._graph_out = self._run(actor, critic, True)
-        torch.cuda.current_stream(dev).wait_stream(s)
-        torch.cuda.synchronize(dev)
+        g, self._graph_out = capture(self.env.device, lambda: self._run(actor, critic, True))
         self.offset = off0   # capture ran nothing
-        self._graph, self._graph_key = g, key
+        self._graphs.store((actor, critic), (), None, g, self.T)
+        return out
 
     def _run(self, actor, critic, dev_offset: bool):
         env, T = self.env, self.T

@@ -541,7 +541,7 @@ def run_idq(steps):
             tg.append(timed(lambda k: col.collect(agent, 0.2, max_steps=G, graph=True), reps) / G)
             host_begin()
             th.append(timed(host_step, G))
-        assert col._graph is not None and bool(col.active.all()), "an env ended inside the measured collect"
+        assert col.captured_graphs() == {None: G} and bool(col.active.all()), "an env ended inside the measured collect"
         print(json.dumps({"config": "idq_collector_step", "envs": E, "agents": A, "packages": P, "steps": G,
                           "collector_step_graph_us": tg, "collector_step_eager_us": te, "host_loop_step_us": th,
                           "graph_spread_us": max(tg) - min(tg), "eager_spread_us": max(te) - min(te),
@@ -700,7 +700,7 @@ def run_qmix_cycle(steps):
             te.append(timed(lambda k: col.step(agent, 0.2), G))
             tg.append(timed(lambda k: col.cycle(agent, 0.2, G, graph=True), reps) / G)
             th.append(timed(host_step, G))
-        assert len(col._graphs) >= 1
+        assert len(col.captured_graphs()) >= 1
         print(json.dumps({"config": "qmix_cycle_step", "envs": E, "agents": A, "packages": P, "steps": G,
                           "max_time_steps": T, "collector_step_graph_us": tg, "collector_step_eager_us": te,
                           "host_loop_step_us": th,

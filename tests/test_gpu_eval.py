@@ -197,7 +197,7 @@ def test_evaluator_greedy_vs_oracle(name):
         ev.delivered.zero_()
         env.load_state(built)
         _same_results(ev.run("greedy", graph=True, graph_steps=7), ep["rewards"], ep["delivered"], ep["steps"])
-        assert ev._graphs is not None and ev._graphs[1] == 7 and ev._graphs[3] == 1, call
+        assert ev.captured_graphs() == {"chunk": 7, "rest": 1}, call
     # the remainder path decides the result when the run stops before every episode is over
     env.load_state(built)
     eager = {k: v.clone() for k, v in mg.Evaluator(env).run("greedy", max_steps=20).items()}
@@ -207,7 +207,7 @@ def test_evaluator_greedy_vs_oracle(name):
     for call in range(2):
         env.load_state(built)
         got = ev.run("greedy", max_steps=20, graph=True, graph_steps=7)
-        assert ev._graphs[1] == 7 and ev._graphs[3] == 6
+        assert ev.captured_graphs() == {"chunk": 7, "rest": 6}
         for k in eager:
             assert torch.equal(got[k], eager[k]), (k, call)
     env.close()
@@ -251,7 +251,7 @@ def test_tape_vs_oracle():
         ev.rewards.zero_()
         env.load_state(built)
         _same_results(ev.run(dev_tape, graph=True), *want)
-    assert ev._graphs[1] == T and ev._graphs[2] is None
+    assert ev.captured_graphs() == {"chunk": T}
     env.load_state(built)
     _same_results(ev.run(dev_tape, max_steps=11), *R.tape_episodes(g, A, P, T, seeds, tape, max_steps=11))
     with pytest.raises(ValueError, match="needs 30"):
@@ -316,7 +316,7 @@ def test_policy_vs_host_driven_loop(deterministic):
     ev = mg.Evaluator(env, seed=5)
     env.load_state(built)
     _same_results(ev.run(policy, deterministic=deterministic, graph=True, graph_steps=16), *want)
-    assert ev._graphs[1] == 16 and ev._graphs[3] == 2
+    assert ev.captured_graphs() == {"chunk": 16, "rest": 2}
     env.load_state(built)
     if deterministic:
         _same_results(ev.run(policy, deterministic=True, graph=True, graph_steps=16), *want)    # a replay
@@ -332,6 +332,30 @@ def test_policy_vs_host_driven_loop(deterministic):
             assert torch.equal(got[k], second[k]), k
         assert ev.offset == two.offset == 100
     env.close()
+
+
+def test_graph_and_eager_sampled_runs_interleave():
+    """Graphed and eager sampled-policy runs on one Evaluator, and an assigned ``offset``, draw exactly
+    what eager runs alone draw (a three-step chunk and a one-step remainder graph per replayed run)."""
+    mg = _mg()
+    E, A, P, T, L = 4, 2, 2, 20, 4
+    env_e, env_o = (mg.BatchedEnv(grid("map.txt"), E, A, P, T, seeds=R.SEEDS[:E], tracker="fresh") for _ in range(2))
+    H, W = env_e.grids[0].shape
+    policy = _LinearActor(H, W, env_e.actor_vec_dim, env_e.device)
+    eager, other = mg.Evaluator(env_e, seed=5), mg.Evaluator(env_o, seed=5)
+    for call, graph in enumerate((True, True, False, True, True)):   # capture, replay, eager, replay, replay
+        if call == 4:
+            other.offset = eager.offset = 1000
+        x = {k: v.clone() for k, v in eager.run(policy, max_steps=L, deterministic=False).items()}
+        y = other.run(policy, max_steps=L, deterministic=False, graph=graph, graph_steps=3)
+        for k in x:
+            assert torch.equal(x[k], y[k]), (call, k)
+        assert torch.equal(eager.actions, other.actions), call
+        assert env_e.save_state().tobytes() == env_o.save_state().tobytes(), call
+        assert eager.offset == other.offset == (1000 + L if call == 4 else (call + 1) * L), call
+    assert other.captured_graphs() == {"chunk": 3, "rest": 1}
+    env_e.close()
+    env_o.close()
 
 
 # ---- 9. refusals

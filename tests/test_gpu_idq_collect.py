@@ -423,7 +423,43 @@ def test_collector_graph_replay_equals_eager(tracker):
             assert bits(getattr(rep_e, k)).tobytes() == bits(getattr(rep_g, k)).tobytes(), f"call {call}: {k}"
         assert env_e.save_state().tobytes() == env_g.save_state().tobytes()
         assert eager.offset == graph.offset == (call + 1) * T and eager.cur == graph.cur
-    assert graph._graph is not None
+    assert graph.captured_graphs() == {None: T}
     assert rep_e.position()[1] == c["capacity"]
     env_e.close()
     env_g.close()
+
+
+def test_graph_and_eager_collects_interleave():
+    """Graphed and eager ``collect`` calls on one collector, and an assigned ``offset``, select exactly
+    what eager calls alone select: the host offset is written to the device before every replay."""
+    import marl_gpu
+    from marl_gpu.idq_rollout import IdqCollector, TransitionReplay
+    c = COLLECT
+    E, A, P, T, n, eps = 4, 2, 2, 20, 4, 0.5   # epsilon 0.5: about half the rows' actions depend on the offset
+    H, W = grid("map.txt").shape
+
+    def make():
+        env = marl_gpu.BatchedEnv(grid("map.txt"), E, A, P, T, seed=c["env_seed"], tracker="fresh")
+        rep = TransitionReplay(29, (6, H, W), device="cuda")   # the ring wraps during the sequence
+        return env, rep, IdqCollector(env, rep, seed=c["seed"], ops_are_ints=True)
+
+    env_e, rep_e, eager = make()
+    env_o, rep_o, other = make()
+    agent = make_agent(H, W)
+    for call, graph in enumerate((True, True, False, True, True)):   # capture, replay, eager, replay, replay
+        if call == 4:
+            other.offset = eager.offset = 1000
+        x = eager.collect(agent, eps, max_steps=n).clone()
+        y = other.collect(agent, eps, max_steps=n, graph=graph).clone()
+        assert bits(x).tobytes() == bits(y).tobytes(), f"call {call}: episode_return"
+        assert rep_e.position() == rep_o.position(), f"call {call}: cursor"
+        for k in ("observations", "next_observations", "actions", "rewards", "dones"):
+            assert bits(getattr(rep_e, k)).tobytes() == bits(getattr(rep_o, k)).tobytes(), f"call {call}: {k}"
+        for k in ("obs", "u", "r_idq", "r_env", "done", "filled", "active"):
+            assert bits(getattr(eager, k)).tobytes() == bits(getattr(other, k)).tobytes(), f"call {call}: {k}"
+        assert env_e.save_state().tobytes() == env_o.save_state().tobytes(), f"call {call}"
+        assert eager.offset == other.offset == (1000 + n if call == 4 else (call + 1) * n), f"call {call}"
+        assert eager.cur == other.cur
+    assert other.captured_graphs() == {None: n}
+    env_e.close()
+    env_o.close()

@@ -422,6 +422,31 @@ def test_collector_graph_replay_equals_eager(tracker):
         assert_batches_equal(x, y, f"call {call}")
         assert env_e.save_state().tobytes() == env_g.save_state().tobytes()
         assert eager.offset == graph.offset == (call + 1) * c["T"]
-    assert graph._graph is not None
+    assert graph.captured_graphs() == {None: c["T"]}
     env_e.close()
     env_g.close()
+
+
+def test_graph_and_eager_collects_interleave():
+    """Graphed and eager ``collect`` calls on one collector, and an assigned ``offset``, select exactly
+    what eager calls alone select: the host offset is written to the device before every replay."""
+    mg, Q = _mg()
+    E, A, P, T, L, eps = 4, 2, 2, 20, 4, 0.5   # epsilon 0.5: about half the rows' actions depend on the offset
+
+    def make():
+        return mg.BatchedEnv(grid("map.txt"), E, A, P, T, seed=COLLECT["env_seed"], tracker="fresh", shaping="qmix")
+
+    env_e, env_o = make(), make()
+    agent = make_agent(env_e.actor_vec_dim)
+    eager, other = Q.QmixCollector(env_e, L, seed=COLLECT["seed"]), Q.QmixCollector(env_o, L, seed=COLLECT["seed"])
+    for call, graph in enumerate((True, True, False, True, True)):   # capture, replay, eager, replay, replay
+        if call == 4:
+            other.offset = eager.offset = 1000
+        x = snapshot(eager.collect(agent, eps))
+        y = snapshot(other.collect(agent, eps, graph=graph))
+        assert_batches_equal(x, y, f"call {call}")
+        assert env_e.save_state().tobytes() == env_o.save_state().tobytes(), f"call {call}"
+        assert eager.offset == other.offset == (1000 + L if call == 4 else (call + 1) * L), f"call {call}"
+    assert other.captured_graphs() == {None: L}
+    env_e.close()
+    env_o.close()

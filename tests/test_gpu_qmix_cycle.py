@@ -431,7 +431,47 @@ def test_cycle_graph_replay_equals_eager(tracker):
         assert same(eager.hidden, graph.hidden) and same(eager.done, graph.done), f"call {call}: hidden / done"
         assert eager.offset == graph.offset == (call + 1) * n and eager.cur == graph.cur
         resets += int(yc.sum())
-    assert len(graph._graphs) == 2          # one graph per starting slot
+    assert graph.captured_graphs() == {0: n, 1: n}   # one graph per starting slot
     assert resets == E, "the calls together pass the time limit once: a replayed graph reset every env"
     env_e.close()
     env_g.close()
+
+
+def test_graph_and_eager_cycles_interleave():
+    """Graphed and eager ``cycle`` calls on one collector, and an assigned ``offset``, select exactly
+    what eager calls alone select."""
+    import marl_gpu
+    from marl_gpu.qmix_cycle import JointReplay, QmixCycleCollector
+    c = COLLECT
+    # epsilon 0.5: about half the rows' actions depend on the offset; an odd cycle alternates the slots
+    E, A, P, T, n, eps = 4, 2, 2, 20, 3, 0.5
+    H, W = grid("map.txt").shape
+
+    def make():
+        env = marl_gpu.BatchedEnv(grid("map.txt"), E, A, P, T, seed=c["env_seed"], tracker="fresh")
+        rep = JointReplay(13, A, (6, H, W), (7, H, W), device="cuda")   # the ring wraps during the sequence
+        col = QmixCycleCollector(env, rep, seed=c["seed"], hidden_dim=c["hidden"])
+        col.begin()
+        return env, rep, col
+
+    env_e, rep_e, eager = make()
+    env_o, rep_o, other = make()
+    agent = GruAgent(H, W, c["hidden"]).cuda()
+    # capture (slot 1), replay, eager, replay, and a replay that first captures slot 0
+    for call, graph in enumerate((True, True, False, True, True)):
+        if call == 4:
+            other.offset = eager.offset = 1000
+        xc, xr = (t.clone() for t in eager.cycle(agent, eps, n))
+        yc, yr = (t.clone() for t in other.cycle(agent, eps, n, graph=graph))
+        assert same(xc, yc) and same(xr, yr), f"call {call}: completed rows"
+        assert rep_e.position() == rep_o.position(), f"call {call}: cursor"
+        for k in ("states", "next_states", "observations", "next_observations", "actions", "total_reward", "dones"):
+            assert same(getattr(rep_e, k), getattr(rep_o, k)), f"call {call}: {k}"
+        assert env_e.save_state().tobytes() == env_o.save_state().tobytes(), f"call {call}: engine state"
+        assert same(eager.hidden, other.hidden) and same(eager.done, other.done), f"call {call}: hidden / done"
+        assert same(eager.u, other.u) and same(eager.explored, other.explored), f"call {call}: actions"
+        assert eager.offset == other.offset == (1000 + n if call == 4 else (call + 1) * n), f"call {call}"
+        assert eager.cur == other.cur
+    assert other.captured_graphs() == {0: n, 1: n}
+    env_e.close()
+    env_o.close()

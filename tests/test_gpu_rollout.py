@@ -192,9 +192,48 @@ def test_graph_rollout_bitwise_equals_eager():
         torch.cuda.synchronize()
         for i, (x, y) in enumerate(zip(a, b)):
             assert torch.equal(x, y), f"rollout {k}, output {i}"
-    assert graphed._graph is not None and eager.offset == graphed.offset
+    assert graphed.captured_graphs() == {None: steps} and eager.offset == graphed.offset
     s0, s1 = env0.read_state(), env1.read_state()
     for key in s0:
         assert torch.equal(s0[key], s1[key]), key
+    env0.close()
+    env1.close()
+
+
+def test_graph_and_eager_rollouts_interleave():
+    """Graphed and eager ``collect`` calls on one rollout, and an assigned ``offset``, draw exactly
+    what eager calls alone draw: the host offset is written to the device before every replay."""
+    mg, R = _mg()
+    g = grid("map.txt")
+    E, A, P, T, steps = 4, 2, 2, 20, 4
+
+    def make():
+        env = mg.BatchedEnv(g, E, A, P, T, seed=7, tracker="mappo", shaping="mappo", max_other_robots=A - 1,
+                            max_packages_obs=5)
+        env.reset()
+        return env
+
+    gen = torch.Generator(device="cuda").manual_seed(3)
+    env0, env1 = make(), make()
+    wa = torch.randn(env0.actor_vec_dim, 15, device="cuda", generator=gen)
+    wc = torch.randn(env0.critic_vec_dim, device="cuda", generator=gen) * 0.01
+
+    def actor(obs, vec):   # the sampled policy: near-uniform logits, so the draw decides the action
+        return vec @ wa * 0.01 + obs.sum(dim=(1, 2, 3)).unsqueeze(1) * 0.01
+
+    def critic(gmap, gvec):
+        return gvec @ wc
+
+    eager, other = R.MappoRollout(env0, steps, seed=5), R.MappoRollout(env1, steps, seed=5)
+    for call, graph in enumerate((True, True, False, True, True)):   # capture, replay, eager, replay, replay
+        if call == 4:
+            other.offset = eager.offset = 1000
+        a = [x.clone() for x in eager.collect(actor, critic)]
+        b = [x.clone() for x in other.collect(actor, critic, graph=graph)]
+        for i, (x, y) in enumerate(zip(a, b)):
+            assert torch.equal(x, y), f"call {call}, output {i}"
+        assert env0.save_state().tobytes() == env1.save_state().tobytes(), f"call {call}"
+        assert eager.offset == other.offset == (1000 + steps if call == 4 else (call + 1) * steps), f"call {call}"
+    assert other.captured_graphs() == {None: steps}
     env0.close()
     env1.close()
