@@ -264,6 +264,30 @@ int mdl_greedy_actions_masked(MdlEngine* eng, const uint8_t* active, uint8_t* ac
  * One launch, one wave per env; touches no state and the engine gains none.  Captures into a hipGraph. */
 int mdl_episode_results(MdlEngine* eng, double* total_reward, int32_t* delivered, int32_t* steps, void* stream);
 
+/* The valid-action mask of every robot, from the engine state: avail DEVICE uint8 [E][A][15], 1 =
+ * available, in the trainer-int column order (column a = move 'D','L','R','S','U'[a % 5], op a / 5;
+ * MAPPO/trainer.py:84-89).  The reference has no counterpart (QMIX/trainer.py:395-397 fills its
+ * avail_u with ones); the rule is pinned against env.step (env.py:173-306).  It describes the state
+ * the next mdl_step acts on.  For robot i at cell c, prop(m) = the neighbour cell of move m, c for S:
+ *   move m is valid:  S always; L/R/U/D iff valid_position(prop(m)) (env.py:197).  Other robots are
+ *                     ignored: collisions are resolved inside the step.
+ *   op 0 is available with every valid move.
+ *   op 1 (pick up) iff the robot carries nothing and a package whose env status is waiting starts
+ *                     at c or at prop(m) (env.py:264-274; waiting implies start_time <= t)
+ *   op 2 (drop)    iff the robot carries package id and that package's target is c or prop(m)
+ *                     (env.py:277-292) -- both cells count, because the robot ends the step on one
+ *                     of them and which one depends on the other robots.
+ *   An invalid move has all three of its columns 0.
+ * So an action is masked exactly when, whatever the other robots do, the step equals the step with
+ * its reduction: the invalid move replaced by S, then the op unavailable under that move by 0.
+ * Column 3 ('S', op 0) is always 1.  Env truth (status bits, package table): the same in both
+ * tracker modes.
+ * active: DEVICE uint8 [E] (mdl_step_episode's mask), read and never written, or NULL.  An env whose
+ *   byte is 0 gets all ones (the reference's placeholder) and nothing of it is loaded; with NULL every
+ *   env is computed, a done one too.
+ * One launch, one wave per env; touches no state and the engine gains none.  Captures into a hipGraph. */
+int mdl_avail_actions(MdlEngine* eng, const uint8_t* active, uint8_t* avail, void* stream);
+
 /* ---- dict-API mailbox: the per-call path of Environment.step / reset on single envs ----
  * Environment.step (env.py:173-306) and VectorizedEnv.step / reset(indices) (QMIX/env_vectorized.py:13-37)
  * return Python dicts per call, so their cost is the host <-> GPU round trip, not the step.  The mailbox
@@ -361,6 +385,20 @@ int mdl_sample_actions(const float* logits, int64_t n_rows, int32_t n_actions, u
 int mdl_sample_actions_dev(const float* logits, int64_t n_rows, int32_t n_actions, uint64_t seed,
                            const uint64_t* offset_dev, uint64_t offset_add, uint8_t* actions, float* log_probs,
                            void* stream);
+
+/* mdl_sample_actions / mdl_sample_actions_dev over the softmax restricted to each row's available
+ * actions.  avail: DEVICE uint8 [n_rows][n_actions] (non-zero = available, mdl_avail_actions' rows),
+ * or NULL = every action available.  The same Philox keying and the same inverse CDF, with the
+ * unavailable actions left out of the maximum, of the sum and of the running sum: an unavailable
+ * action has probability exactly 0 and is never returned, and log_probs is the log of the
+ * renormalised probability, (l_a - max_avail) - log(sum_avail exp(l_i - max_avail)).  A row with no
+ * available action gets action 0 and log-prob -inf.  With avail NULL or all non-zero, actions and
+ * log-probs are bit for bit mdl_sample_actions' at the same (seed, offset). */
+int mdl_sample_actions_avail(const float* logits, const uint8_t* avail, int64_t n_rows, int32_t n_actions,
+                             uint64_t seed, uint64_t offset, uint8_t* actions, float* log_probs, void* stream);
+int mdl_sample_actions_avail_dev(const float* logits, const uint8_t* avail, int64_t n_rows, int32_t n_actions,
+                                 uint64_t seed, const uint64_t* offset_dev, uint64_t offset_add, uint8_t* actions,
+                                 float* log_probs, void* stream);
 
 /* Epsilon-greedy action selection over Q-values (QMIX/trainer.py:298-319), the library's random
  * stream in place of torch's.  q: float32 [n_rows][n_actions]; avail: uint8 of the same shape

@@ -954,6 +954,13 @@ int mdl_episode_results(MdlEngine* eng, double* total_reward, int32_t* delivered
     return 0;
 }
 
+int mdl_avail_actions(MdlEngine* eng, const uint8_t* active, uint8_t* avail, void* stream) {
+    if (!eng || !avail) return fail("mdl_avail_actions: null argument");
+    DeviceGuard dg(eng->device);
+    HIPCHK(mdl::launch_avail_actions(eng->p, active, avail, (hipStream_t)stream));
+    return 0;
+}
+
 // ---- checkpoint ----
 namespace {
 constexpr uint32_t CKPT_VERSION = 2;

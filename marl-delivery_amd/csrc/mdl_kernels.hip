@@ -10,6 +10,7 @@
 //   k_views_*      the same builders / shaping fed from packed dict views
 //   k_export       int32 snapshot of the SoA state
 //   k_episode_results  total_reward, delivered count and t per env   evaluation.py:49-51
+//   k_avail_actions    the valid-action mask of every robot, from the engine state
 //
 // One wavefront per env; `wpb` envs per 256-thread workgroup, each with its
 // own LDS slice of `lds_stride` bytes (dynamic shared memory).  Waves never
@@ -1976,6 +1977,93 @@ __global__ __launch_bounds__(256) void k_episode_results(DevParams p, double* __
     }
 }
 
+// ------------------------------------------------------- valid-action mask
+// Which of the 15 trainer-int actions (column a = move D,L,R,S,U[a % 5], op a / 5) can differ from
+// a simpler one in the state the next step acts on (include/mdl_engine.h states the rule): uint8
+// [E][A][15].  One wave per env, robots on lanes, no LDS and no workgroup barrier.  A move is valid
+// by the robot word's bits 27-30.  Pick-up: the state words come in chunks of 64 slots, one per
+// lane; for a chunk that holds a waiting package, every robot that carries nothing is taken in turn
+// (its cell broadcast by readlane) and one v_sad_u8 per lane finds the waiting packages that start
+// on the cell or next to it -- a miss, the common case, costs that and a ballot; a hit is resolved
+// into the five candidate cells by five ballots.  Drop: the carrying robot's lane takes its
+// package's target from the lane that holds slot carry - 1 (ds_bpermute, no dependent load).  Each
+// robot's lane stores its 15 bytes.  No load waits for another one: the robot words go out with
+// the first chunk's words, the next chunk's while a chunk is worked on.  An env whose byte of
+// `active` is 0 gets ones and loads nothing else.  Touches no state.
+__global__ __launch_bounds__(256) void k_avail_actions(DevParams p, const uint8_t* __restrict__ active,
+                                                       uint8_t* __restrict__ avail) {
+    const int lane = lane_id();
+    const int e = xcd_block() * 4 + wave_id();
+    if (e >= p.E) return;
+    const int A = p.A, P = p.P;
+    uint8_t* o = avail + ((size_t)e * A + lane) * 15;
+    if (active && !active[e]) {
+        if (lane < A) {
+#pragma unroll
+            for (int c = 0; c < 15; c++) o[c] = 1;
+        }
+        return;
+    }
+    // the robot words and the first chunk's state and package words are issued together (they do
+    // not depend on each other); a later chunk's are loaded while the one before it is worked on
+    const uint16_t* ps = p.pstate + (size_t)e * P;
+    const uint64_t* pk = p.pkg + (size_t)e * P;
+    const uint32_t rv = lane < A ? p.rob[(size_t)e * A + lane] : 0u;
+    uint32_t f = lane < P ? ps[lane] : 0u;       // a lane past P holds 0: ST_NONE
+    uint64_t d = lane < P ? pk[lane] : 0ull;
+    const int cell = rob_cell(rv), carry = rob_carry(rv);
+    const uint32_t valid = rob_valid(rv) | 1u;   // bit m: move code m (S 0, L 1, R 2, U 3, D 4) is valid
+    constexpr int DELTA[5] = {0, -256, 256, -1, 1};   // packed-cell delta of each move code
+    const bool carries = lane < A && carry >= 1 && carry <= P;
+    int tg = 0;   // the carried package's target, taken from the lane that holds slot carry - 1
+    // pick: bit m set if a waiting package starts on the cell move m proposes
+    uint32_t pick = 0;
+    const uint64_t free_hands = ballot(lane < A && carry == 0);
+    for (int j0 = 0; j0 < P; j0 += WAVE) {
+        const int jn = j0 + WAVE + lane;
+        const uint32_t fn = jn < P ? ps[jn] : 0u;
+        const uint64_t dn = jn < P ? pk[jn] : 0ull;
+        const bool waiting = (f & PS_STATUS) == ST_WAITING;
+        const int start = pk_start(d);
+        const int src = carry - 1 - j0;
+        const int tsrc = __builtin_amdgcn_ds_bpermute((src & 63) << 2, pk_target(d));
+        if (carries && src >= 0 && src < WAVE) tg = tsrc;
+        if (ballot(waiting)) {
+            for (uint64_t todo = free_hands; todo; todo &= todo - 1) {
+                const int a = ffs64(todo);
+                const int ca = rdl(cell, a);
+                const bool near = waiting && manhattan_sad(start, ca) <= 1;
+                if (!ballot(near)) continue;
+                uint32_t bits = 0;
+#pragma unroll
+                for (int m = 0; m < 5; m++) bits |= ballot(near && start == ca + DELTA[m]) ? 1u << m : 0u;
+                if (lane == a) pick |= bits;
+            }
+        }
+        f = fn;
+        d = dn;
+    }
+    // drop: bit m set if the carried package's target is the cell move m proposes
+    uint32_t drop = 0;
+    if (carries) {
+#pragma unroll
+        for (int m = 0; m < 5; m++) drop |= tg == cell + DELTA[m] ? 1u << m : 0u;
+    }
+    if (lane < A) {
+        const uint32_t can = carry == 0 ? pick : drop;   // the op this robot can do at all, per cell
+        const int can_op = carry == 0 ? 1 : 2;
+#pragma unroll
+        for (int c = 0; c < 15; c++) {
+            const int m = (0x30214 >> (4 * (c % 5))) & 0xf;   // D,L,R,S,U -> move codes 4,1,2,0,3
+            const int op = c / 5;
+            const bool mv_ok = (valid >> m) & 1u;
+            // the robot ends the step on its own cell or on the proposed one
+            const bool op_ok = op == 0 || (op == can_op && (((can >> m) | can) & 1u));
+            o[c] = mv_ok && op_ok ? 1 : 0;
+        }
+    }
+}
+
 // ------------------------------------------------------- dict-API mailbox export
 // The rows of the envs a dict-API call touched (row w = env ids[w], or env w without ids),
 // written straight into the engine's host-mapped mailbox (no device staging buffer, no copy
@@ -2429,6 +2517,11 @@ hipError_t launch_export(const DevParams& p, int32_t* robots, int32_t* pkgs, int
 hipError_t launch_episode_results(const DevParams& p, double* total, int32_t* delivered, int32_t* steps,
                                   hipStream_t s) {
     hipLaunchKernelGGL(k_episode_results, dim3(blocks_for(p.E, 4)), dim3(256), 0, s, p, total, delivered, steps);
+    return hipGetLastError();
+}
+
+hipError_t launch_avail_actions(const DevParams& p, const uint8_t* active, uint8_t* avail, hipStream_t s) {
+    hipLaunchKernelGGL(k_avail_actions, dim3(blocks_for(p.E, 4)), dim3(256), 0, s, p, active, avail);
     return hipGetLastError();
 }
 

@@ -115,6 +115,8 @@ hipError_t launch_export(const DevParams& p, int32_t* robots, int32_t* pkgs, int
 // k_episode_results over all p.E envs: total_reward, delivered package slots, t (each may be null)
 hipError_t launch_episode_results(const DevParams& p, double* total, int32_t* delivered, int32_t* steps,
                                   hipStream_t s);
+// k_avail_actions over all p.E envs: uint8 [E][A][15]; active (device uint8 [E]) may be null
+hipError_t launch_avail_actions(const DevParams& p, const uint8_t* active, uint8_t* avail, hipStream_t s);
 
 // Greedy agent record layout (mdl_greedy.hip): per env `stride` bytes.
 struct GreedyLayout {

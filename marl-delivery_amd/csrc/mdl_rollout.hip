@@ -5,6 +5,7 @@
 //   k_sample  Categorical(logits).sample() + log_prob   MAPPO/trainer.py:141-143
 //             (inverse CDF of softmax(logits) on a Philox4x32-10 uniform;
 //             the stream is this library's own, keyed by (seed, offset, row))
+//   k_sample_avail  k_sample over the available actions of each row (a valid-action mask)
 //   k_select_eps  epsilon-greedy selection over Q-values   QMIX/trainer.py:298-319
 //             (the same Philox keying; include/mdl_engine.h states the draw)
 //   k_gae     the GAE recursion of MAPPO/trainer.py:266-276, same float32
@@ -73,6 +74,53 @@ __global__ __launch_bounds__(256) void k_sample(const float* __restrict__ logits
         if (a < 0 && target < cum) a = i;
     }
     if (a < 0) a = last;  // u*S rounded up to the full sum
+    actions[row] = (uint8_t)a;
+    if (log_probs) log_probs[row] = (m == -INFINITY) ? -INFINITY : (l[a] - m) - logf(S);
+}
+
+// k_sample over the softmax restricted to the row's available actions (avail uint8 [n_rows][n_act],
+// non-zero = available): the same Philox block, the same sequential fp32 sums and the same inverse
+// CDF, with every unavailable action left out of the maximum, of S and of the running sum, so its
+// probability is exactly 0 and it is never returned; log_prob = (l_a - max) - log(S) over the
+// available actions.  With every action available each operation is k_sample's, in its order: the
+// same bits.  A row with no available action gets action 0, a row whose available logits are all
+// -inf its first available action (k_sample's 0 when all are), both with log_prob -inf.
+__global__ __launch_bounds__(256) void k_sample_avail(const float* __restrict__ logits,
+                                                      const uint8_t* __restrict__ avail, int64_t n_rows, int n_act,
+                                                      uint32_t k0, uint32_t k1, uint32_t off_lo, uint32_t off_hi,
+                                                      const uint64_t* __restrict__ off_dev,
+                                                      uint8_t* __restrict__ actions, float* __restrict__ log_probs) {
+    const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= n_rows) return;
+    if (off_dev) {
+        const uint64_t o = *off_dev + ((uint64_t)off_hi << 32 | off_lo);
+        off_lo = (uint32_t)o;
+        off_hi = (uint32_t)(o >> 32);
+    }
+    const float* l = logits + row * n_act;
+    const uint8_t* av = avail + row * n_act;
+    float m = -INFINITY;
+    for (int i = 0; i < n_act; i++)
+        if (av[i]) m = fmaxf(m, l[i]);
+    float S = 0.0f;
+    for (int i = 0; i < n_act; i++)
+        if (av[i]) S = S + expf(l[i] - m);
+    uint32_t c[4] = {off_lo, off_hi, (uint32_t)row, (uint32_t)(row >> 32)};
+    philox4x32_10(c, k0, k1);
+    const float u = (float)(c[0] >> 8) * 0x1p-24f;
+    const float target = u * S;
+    int a = -1, last = -1, first_av = -1;
+    float cum = 0.0f;
+    for (int i = 0; i < n_act; i++) {
+        if (!av[i]) continue;
+        const float ei = expf(l[i] - m);
+        cum = cum + ei;
+        if (first_av < 0) first_av = i;
+        if (ei > 0.0f) last = i;
+        if (a < 0 && target < cum) a = i;
+    }
+    // u*S rounded up to the full sum: the last action with weight, as k_sample
+    if (a < 0) a = last >= 0 ? last : (first_av >= 0 ? first_av : 0);
     actions[row] = (uint8_t)a;
     if (log_probs) log_probs[row] = (m == -INFINITY) ? -INFINITY : (l[a] - m) - logf(S);
 }
@@ -332,7 +380,7 @@ int rfail(const char* msg, hipError_t e = hipSuccess) {
 
 extern "C" {
 
-static int sample(const char* what, const float* logits, int64_t n_rows, int32_t n_actions, uint64_t seed,
+static int sample(const char* what, const float* logits, const uint8_t* avail, int64_t n_rows, int32_t n_actions, uint64_t seed,
                   uint64_t offset, const uint64_t* offset_dev, uint8_t* actions, float* log_probs, void* stream) {
     char msg[96];
     if (!logits || !actions) {
@@ -345,9 +393,14 @@ static int sample(const char* what, const float* logits, int64_t n_rows, int32_t
     }
     if (n_rows == 0) return 0;
     const int64_t blocks = (n_rows + 255) / 256;
-    hipLaunchKernelGGL(mdl::k_sample, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, logits, n_rows,
-                       (int)n_actions, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)offset,
-                       (uint32_t)(offset >> 32), offset_dev, actions, log_probs);
+    if (avail)
+        hipLaunchKernelGGL(mdl::k_sample_avail, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, logits,
+                           avail, n_rows, (int)n_actions, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)offset,
+                           (uint32_t)(offset >> 32), offset_dev, actions, log_probs);
+    else
+        hipLaunchKernelGGL(mdl::k_sample, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, logits, n_rows,
+                           (int)n_actions, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)offset,
+                           (uint32_t)(offset >> 32), offset_dev, actions, log_probs);
     const hipError_t e = hipGetLastError();
     if (e == hipSuccess) return 0;
     snprintf(msg, sizeof msg, "%s: launch failed", what);
@@ -356,15 +409,30 @@ static int sample(const char* what, const float* logits, int64_t n_rows, int32_t
 
 int mdl_sample_actions(const float* logits, int64_t n_rows, int32_t n_actions, uint64_t seed, uint64_t offset,
                        uint8_t* actions, float* log_probs, void* stream) {
-    return sample("mdl_sample_actions", logits, n_rows, n_actions, seed, offset, nullptr, actions, log_probs, stream);
+    return sample("mdl_sample_actions", logits, nullptr, n_rows, n_actions, seed, offset, nullptr, actions, log_probs,
+                  stream);
 }
 
 int mdl_sample_actions_dev(const float* logits, int64_t n_rows, int32_t n_actions, uint64_t seed,
                            const uint64_t* offset_dev, uint64_t offset_add, uint8_t* actions, float* log_probs,
                            void* stream) {
     if (!offset_dev) return rfail("mdl_sample_actions_dev: null argument");
-    return sample("mdl_sample_actions_dev", logits, n_rows, n_actions, seed, offset_add, offset_dev, actions,
+    return sample("mdl_sample_actions_dev", logits, nullptr, n_rows, n_actions, seed, offset_add, offset_dev, actions,
                   log_probs, stream);
+}
+
+int mdl_sample_actions_avail(const float* logits, const uint8_t* avail, int64_t n_rows, int32_t n_actions,
+                             uint64_t seed, uint64_t offset, uint8_t* actions, float* log_probs, void* stream) {
+    return sample("mdl_sample_actions_avail", logits, avail, n_rows, n_actions, seed, offset, nullptr, actions,
+                  log_probs, stream);
+}
+
+int mdl_sample_actions_avail_dev(const float* logits, const uint8_t* avail, int64_t n_rows, int32_t n_actions,
+                                 uint64_t seed, const uint64_t* offset_dev, uint64_t offset_add, uint8_t* actions,
+                                 float* log_probs, void* stream) {
+    if (!offset_dev) return rfail("mdl_sample_actions_avail_dev: null argument");
+    return sample("mdl_sample_actions_avail_dev", logits, avail, n_rows, n_actions, seed, offset_add, offset_dev,
+                  actions, log_probs, stream);
 }
 
 static int select_eps(const char* what, const float* q, const uint8_t* avail, int64_t n_rows, int32_t n_actions,

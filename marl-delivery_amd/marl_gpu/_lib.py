@@ -92,6 +92,7 @@ SIGNATURES = {
     "mdl_greedy_actions": (C.c_int, [_vp, _vp, _i32, _vp, _vp]),
     "mdl_greedy_actions_masked": (C.c_int, [_vp, _vp, _vp, _vp]),
     "mdl_episode_results": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "mdl_avail_actions": (C.c_int, [_vp, _vp, _vp, _vp]),
     "mdl_mailbox": (C.c_int, [_vp, C.POINTER(MdlMailbox)]),
     "mdl_mail_step": (C.c_int, [_vp, _i32, _i32, _i32, _vp]),
     "mdl_mail_reset": (C.c_int, [_vp, _i32, _i32, _vp]),
@@ -103,6 +104,8 @@ SIGNATURES = {
     "mdl_load_state": (C.c_int, [_vp, _vp, C.c_int64, _vp]),
     "mdl_sample_actions": (C.c_int, [_vp, C.c_int64, _i32, C.c_uint64, C.c_uint64, _vp, _vp, _vp]),
     "mdl_sample_actions_dev": (C.c_int, [_vp, C.c_int64, _i32, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp]),
+    "mdl_sample_actions_avail": (C.c_int, [_vp, _vp, C.c_int64, _i32, C.c_uint64, C.c_uint64, _vp, _vp, _vp]),
+    "mdl_sample_actions_avail_dev": (C.c_int, [_vp, _vp, C.c_int64, _i32, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp]),
     "mdl_select_actions_eps": (C.c_int, [_vp, _vp, C.c_int64, _i32, C.c_float, C.c_uint64, C.c_uint64, _vp, _vp]),
     "mdl_select_actions_eps_dev": (C.c_int, [_vp, _vp, C.c_int64, _i32, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp]),
     "mdl_select_actions_eps_mark": (C.c_int, [_vp, _vp, C.c_int64, _i32, C.c_float, C.c_uint64, C.c_uint64, _vp, _vp,

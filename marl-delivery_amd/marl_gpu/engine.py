@@ -22,6 +22,7 @@ import torch
 from . import _lib
 from ._lib import check, lib, ptr, stream_handle
 from ._lib import raw_stream as _raw_stream
+from .actions import ACTION_DIM
 from .maps import grid_array, load_map, map_path
 
 # shaping constants, order: pickup, on_time, late, closer, wasted_pick,
@@ -670,6 +671,28 @@ class BatchedEnv:
         check(lib().mdl_episode_results(self._h, ptr(out[0]), ptr(out[1]), ptr(out[2]), self._stream()),
               "mdl_episode_results")
         return out[0], out[1], out[2]
+
+    def avail_actions(self, active=None, out=None) -> torch.Tensor:
+        """The valid-action mask of every robot in the state the next step acts on: uint8
+        [E, A, 15], 1 = available, columns in the trainer-int order (move 'DLRSU'[a % 5], op a // 5).
+        A move into a wall or off the map, a pick-up with nothing waiting on the robot's cell or the
+        proposed one (or with a package already carried), and a drop whose target is neither cell
+        (or with nothing carried) are 0: each is certain to equal a simpler action, whatever the
+        other robots do (include/mdl_engine.h, ``mdl_avail_actions``, states the rule).  ('S', 0)
+        is always 1.  ``active`` (uint8 [E] on the device, ``step_episode``'s mask; read, never
+        written): an env whose byte is 0 gets all ones; None: every env is computed.  ``out``: a
+        contiguous uint8 tensor [E, A, 15] on the engine's device.  One launch, no host round trip;
+        touches no state."""
+        if active is not None:
+            self._check_mask(active, "active")
+        shape = (self.E, self.A, ACTION_DIM)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or not out.is_cuda \
+                or not out.is_contiguous() or tuple(out.shape) != shape or out.get_device() != self.device.index:
+            raise ValueError(f"out must be a contiguous uint8 tensor {list(shape)} on {self.device}")
+        check(lib().mdl_avail_actions(self._h, ptr(active), ptr(out), self._stream()), "mdl_avail_actions")
+        return out
 
     # ---- checkpoint (SURVEY.md §8(f)4): engine state incl. every env's MT19937 stream ----
     def save_state(self, path=None) -> np.ndarray:

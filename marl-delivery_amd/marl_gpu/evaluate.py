@@ -16,7 +16,7 @@ import torch
 
 from ._capture import Graphed, capture, eval_mode
 from ._lib import check, lib, ptr, stream_handle
-from .actions import sample_actions, sample_actions_dev, select_actions_eps
+from .actions import ACTION_DIM, sample_actions, sample_actions_dev, select_actions_eps
 
 # randomagent.py:16-17 in the engine's action codes (move code | op << 3)
 _RANDOM_MOVES = np.array([3, 4, 1, 2, 0], np.uint8)   # 'U', 'D', 'L', 'R', 'S'
@@ -98,6 +98,8 @@ class Evaluator(Graphed):
         self.steps = torch.zeros(E, dtype=torch.int32, device=dev)
         self._log_probs = torch.zeros(E * A, dtype=torch.float32, device=dev)   # the sampler's second output
         self._obs = None              # the policy's observation buffers, used in place
+        self.avail = None             # uint8 [E, A, 15], the last step's mask of a run with avail=True
+        self._masked = False
 
     # ------------------------------------------------------------------ results
     def results(self) -> dict:
@@ -126,12 +128,15 @@ class Evaluator(Graphed):
 
     @torch.no_grad()
     def run(self, agent, max_steps: int | None = None, deterministic: bool = True, graph: bool = False,
-            graph_steps: int = 50) -> dict:
+            graph_steps: int = 50, avail: bool = False) -> dict:
         """One episode of at most L = min(max_steps or env.T, env.T) steps in every env, from a fresh
         reset; returns ``results()``.  deterministic (policies only): the lowest index among the
         largest logits (``select_actions_eps`` at epsilon 0); otherwise ``sample_actions`` at
         (seed, offset), the offset advancing by one per step.  A policy module runs in eval mode
-        and its mode is restored.
+        and its mode is restored.  avail (policies only): the selection, or the sampler, takes the
+        valid-action mask of each state (``BatchedEnv.avail_actions`` with the running-env mask, one
+        small launch per step), so the policy never plays an action that is certain to equal a
+        simpler one.
 
         graph=True: the first call runs eagerly, then captures min(L, graph_steps) steps as one
         hipGraph (and the L mod chunk remaining steps as a second one); later calls with the same
@@ -153,6 +158,7 @@ class Evaluator(Graphed):
                     or not agent.is_contiguous():
                 raise TypeError(f"Evaluator: an action tape must be a contiguous uint8 tensor on {env.device}")
         det = bool(deterministic)
+        self._masked = bool(avail) and kind == "policy"
         with eval_mode(agent):
             if not graph:
                 self._begin(kind)
@@ -163,7 +169,7 @@ class Evaluator(Graphed):
             if chunk < 1:
                 raise ValueError("Evaluator: graph_steps must be >= 1")
             # a graph reads the agent's parameters (or the tape) in place: replay only for the very same object
-            owners, values = (agent,), (kind, L, chunk, det)
+            owners, values = (agent,), (kind, L, chunk, det, self._masked)
             g = self._graphs.lookup(owners, values, "chunk")
             self._begin(kind)
             if g is not None:
@@ -195,6 +201,8 @@ class Evaluator(Graphed):
                 self._obs = dict(actor_map=torch.empty((env.E, env.A, 6, H, W), **f),
                                  actor_vec=torch.empty((env.E, env.A, env.actor_vec_dim), **f))
             env.build_obs(out=self._obs, which=("actor_map", "actor_vec"))
+            if self._masked and self.avail is None:
+                self.avail = torch.ones((env.E, env.A, ACTION_DIM), dtype=torch.uint8, device=env.device)
 
     def _steps(self, kind, agent, k0, n, deterministic, dev_offset):
         """Steps k0 .. k0+n-1 of the run.  dev_offset (under capture): the sampler's offset is the
@@ -211,12 +219,13 @@ class Evaluator(Graphed):
                 om, ov = self._obs["actor_map"], self._obs["actor_vec"]
                 logits = agent(om.reshape(E * A, *om.shape[2:]), ov.reshape(E * A, -1))
                 acts = self.actions.view(-1)
+                av = env.avail_actions(self.active, out=self.avail) if self._masked else None
                 if deterministic:
-                    select_actions_eps(logits, 0.0, self.seed, 0, out=acts)
+                    select_actions_eps(logits, 0.0, self.seed, 0, avail=av, out=acts)
                 elif dev_offset:
-                    sample_actions_dev(logits, self.seed, self._off_dev, k, out=(acts, self._log_probs))
+                    sample_actions_dev(logits, self.seed, self._off_dev, k, out=(acts, self._log_probs), avail=av)
                 else:
-                    sample_actions(logits, self.seed, self.offset, out=(acts, self._log_probs))
+                    sample_actions(logits, self.seed, self.offset, out=(acts, self._log_probs), avail=av)
                     self.offset += 1
                 env.step_episode(self.actions, self.active, action_format="int", obs_out=self._obs,
                                  which=("actor_map", "actor_vec"))

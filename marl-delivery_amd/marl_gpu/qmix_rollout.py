@@ -38,12 +38,19 @@ class QmixCollector(Graphed):
     Rows of an env past its episode's end (filled == 0) are not written: they hold whatever
     an earlier collect left there.
 
+    avail=True: the selection takes the valid-action mask of each state (``BatchedEnv.avail_actions``,
+    one small launch per step, inside the graph too) instead of the reference's all-ones placeholder
+    (QMIX/trainer.py:395-397), and ``batch()`` gains avail uint8 [L+1, E, A, n_actions]: slot t = the
+    mask the selection of step t used, slot t+1 = the mask after it (all ones for an env whose episode
+    has ended: every slot is written).  ``EpisodeReplay`` stores it and returns it as avail_u /
+    avail_u_next.  avail=False (the default): nothing changes.
+
     One deviation from the reference: the agent also runs on the finished envs (the
     reference shrinks its batch instead).  Their actions and hidden states are ignored --
     the engine does not step them -- so the finished envs cost forward-pass time only.
     """
 
-    def __init__(self, env, episode_limit: int, seed: int = 0):
+    def __init__(self, env, episode_limit: int, seed: int = 0, avail: bool = False):
         self.env = env
         self.L = L = min(int(episode_limit), env.T)
         if L < 1:
@@ -70,15 +77,19 @@ class QmixCollector(Graphed):
         self.episode_return = torch.zeros(E, dtype=torch.float64, device=dev)
         self.episode_length = torch.zeros(E, dtype=torch.int64, device=dev)
         self._eps_dev = torch.zeros(1, **f)
+        self.avail = torch.ones((L + 1, E, A, ACTION_DIM), **b) if avail else None
 
     def _slot(self, k):
         return dict(actor_map=self.so[k], actor_vec=self.vo[k], critic_map=self.gs[k], critic_vec=self.gv[k])
 
     def batch(self):
         """The buffers of the last collect (the collector's own tensors, not copies)."""
-        return dict(so=self.so, vo=self.vo, gs=self.gs, gv=self.gv, u=self.u, r=self.r, r64=self.r64,
-                    r_shaped=self.r_shaped, terminated=self.terminated, filled=self.filled, hidden=self.hidden,
-                    episode_return=self.episode_return, episode_length=self.episode_length)
+        out = dict(so=self.so, vo=self.vo, gs=self.gs, gv=self.gv, u=self.u, r=self.r, r64=self.r64,
+                   r_shaped=self.r_shaped, terminated=self.terminated, filled=self.filled, hidden=self.hidden,
+                   episode_return=self.episode_return, episode_length=self.episode_length)
+        if self.avail is not None:
+            out["avail"] = self.avail
+        return out
 
     @torch.no_grad()
     def collect(self, agent, epsilon: float, graph: bool = False):
@@ -116,6 +127,9 @@ class QmixCollector(Graphed):
             env.clear_tracker()
         self.active.fill_(1)
         env.build_obs(out=self._slot(0))
+        masks = self.avail
+        if masks is not None:
+            env.avail_actions(self.active, out=masks[0])
         h0 = agent.init_hidden()
         h0 = h0.reshape(1, -1).to(device=env.device, dtype=torch.float32)
         if self.hidden is None:
@@ -124,13 +138,16 @@ class QmixCollector(Graphed):
         for t in range(L):
             so = self.so[t]
             q, h = agent(so.reshape(E * A, *so.shape[2:]), self.vo[t].reshape(E * A, -1), h)
+            av = None if masks is None else masks[t]
             if dev_args:
-                select_actions_eps_dev(q, self._eps_dev, self.seed, self._off_dev, t, out=self.u[t].view(-1))
+                select_actions_eps_dev(q, self._eps_dev, self.seed, self._off_dev, t, avail=av, out=self.u[t].view(-1))
             else:
-                select_actions_eps(q, epsilon, self.seed, self.offset, out=self.u[t].view(-1))
+                select_actions_eps(q, epsilon, self.seed, self.offset, avail=av, out=self.u[t].view(-1))
             self.offset += 1
             env.step_episode(self.u[t], self.active, out=(self.r64[t], self.r_shaped[t], self.terminated[t]),
                              filled=self.filled[t], obs_out=self._slot(t + 1))
+            if masks is not None:
+                env.avail_actions(self.active, out=masks[t + 1])
         if dev_args:
             check(lib().mdl_counter_add(ptr(self._off_dev), L, stream_handle(env.device)), "mdl_counter_add")
         self.hidden.copy_(h)

@@ -178,7 +178,9 @@ class EpisodeReplay:
     of ``capacity`` episodes in plain torch ops, on the device of the template's tensors.
 
     ``collector``: a ``QmixCollector`` or one of its batches (a dict with so, vo, gs, gv, u, r,
-    terminated, filled) -- the template for shapes, dtypes and device.
+    terminated, filled) -- the template for shapes, dtypes and device.  A template with an
+    ``avail`` field (uint8 [L+1, E, A, n_actions], ``QmixCollector(avail=True)``) makes the ring
+    store the valid-action masks too (``self.fields``; ``FIELDS`` is the reference's set).
 
     ``add`` stores a batch's E episodes in env order; the reference stores each episode when it
     terminates, i.e. in termination order.  Only the eviction order inside one batch differs.
@@ -192,8 +194,9 @@ class EpisodeReplay:
             raise ValueError("EpisodeReplay: capacity must be >= 1")
         self.n_actions = int(n_actions)
         tpl = collector if isinstance(collector, dict) else collector.batch()
+        self.fields = self.FIELDS + (("avail",) if tpl.get("avail") is not None else ())
         self.buf = {}
-        for k in self.FIELDS:
+        for k in self.fields:
             t = tpl[k]
             self.buf[k] = torch.zeros((t.shape[0], self.capacity) + tuple(t.shape[2:]), dtype=t.dtype, device=t.device)
         self.L = tpl["u"].shape[0]
@@ -211,7 +214,7 @@ class EpisodeReplay:
         first = max(0, E - self.capacity)   # a batch larger than the ring keeps its last `capacity` episodes
         slots = (torch.arange(first, E) + self.idx) % self.capacity
         slots = slots.to(self.device)
-        for k in self.FIELDS:
+        for k in self.fields:
             self.buf[k][:, slots] = batch[k][:, first:]
         self.idx = (self.idx + E) % self.capacity
         self.size = min(self.capacity, self.size + E)
@@ -220,8 +223,10 @@ class EpisodeReplay:
         """``batch_size`` distinct stored episodes as the reference's dictionary
         (QMIX/networks.py:299-314), episode-major: so / vo / gs / gv and their ``_next`` forms
         ([B, L, ...]; ``*_next`` is the same gathered tensor shifted by one slot, not a second
-        copy), u int64 [B, L, A, 1], r [B, L, 1], avail_u / avail_u_next (all ones, [B, L, A,
-        n_actions]), terminated and padded (= 1 - filled) float32 [B, L, 1]."""
+        copy), u int64 [B, L, A, 1], r [B, L, 1], avail_u / avail_u_next float32 [B, L, A,
+        n_actions] (the stored masks of slots 0..L-1 and 1..L, two views of one gather, when the
+        ring stores ``avail``; otherwise all ones, as QMIX/trainer.py:395-397 fills them),
+        terminated and padded (= 1 - filled) float32 [B, L, 1]."""
         B = int(batch_size)
         if B < 1 or self.size < B:
             raise ValueError(f"EpisodeReplay holds {self.size} episodes, cannot sample {B}")
@@ -235,9 +240,14 @@ class EpisodeReplay:
         A = self.buf["u"].shape[2]
         out["u"] = self.buf["u"][:, idx].transpose(0, 1).long().unsqueeze(-1)
         out["r"] = self.buf["r"][:, idx].transpose(0, 1).unsqueeze(-1)
-        ones = torch.ones((), dtype=torch.float32, device=self.device).expand(B, L, A, self.n_actions)
-        out["avail_u"] = ones
-        out["avail_u_next"] = ones
+        if "avail" in self.buf:
+            av = self.buf["avail"][:, idx].transpose(0, 1).float()   # [B, L+1, A, n_actions]
+            out["avail_u"] = av[:, :L]
+            out["avail_u_next"] = av[:, 1:]
+        else:
+            ones = torch.ones((), dtype=torch.float32, device=self.device).expand(B, L, A, self.n_actions)
+            out["avail_u"] = ones
+            out["avail_u_next"] = ones
         out["terminated"] = self.buf["terminated"][:, idx].transpose(0, 1).float().unsqueeze(-1)
         out["padded"] = 1.0 - self.buf["filled"][:, idx].transpose(0, 1).float().unsqueeze(-1)
         return out

@@ -49,9 +49,16 @@ class MappoRollout(Graphed):
     max_other_robots=A-1, max_packages_obs=5, auto-reset on done).  actor(obs [E*A,6,H,W],
     vec [E*A,Dv]) -> logits [E*A, 15]; critic(gmap [E,4,H,W], gvec [E,Dg]) -> values [E]
     or [E, 1].  ``collect`` returns the reference's flattened batch.
+
+    avail=True: each step's sampler takes the valid-action mask of the current state
+    (``BatchedEnv.avail_actions``; ``sample_actions(avail=)``: the draw and the log-prob are those of
+    the softmax over the available actions), and the masks are kept in ``mb_avail`` uint8
+    [T, E, A, 15] so a learner applies the same mask when it recomputes log-probs.  The returned batch
+    is unchanged in form.  avail=False (the default): nothing changes.
     """
 
-    def __init__(self, env, rollout_steps: int, seed: int = 0, gamma: float = 0.99, gae_lambda: float = 0.95):
+    def __init__(self, env, rollout_steps: int, seed: int = 0, gamma: float = 0.99, gae_lambda: float = 0.95,
+                 avail: bool = False):
         self.env = env
         self.T = int(rollout_steps)
         self.seed = int(seed)
@@ -74,6 +81,7 @@ class MappoRollout(Graphed):
         self.next_obs = env.obs_buffers(E, H, W)
         self._r_env = torch.zeros(E, dtype=torch.float64, device=dev)
         self._graph_out = None
+        self.mb_avail = torch.ones((T, E, A, ACTION_DIM), dtype=torch.uint8, device=dev) if avail else None
 
     def _slot(self, k):
         return dict(actor_map=self.mb_obs[k], actor_vec=self.mb_vector_obs[k], critic_map=self.mb_global_states[k],
@@ -108,10 +116,11 @@ class MappoRollout(Graphed):
             obs = self.mb_obs[step]
             logits = actor(obs.reshape(E * A, *obs.shape[2:]), self.mb_vector_obs[step].reshape(E * A, -1))
             acts_lp = (self.mb_actions[step].view(-1), self.mb_log_probs[step].view(-1))
+            av = None if self.mb_avail is None else env.avail_actions(out=self.mb_avail[step])
             if dev_offset:
-                sample_actions_dev(logits, self.seed, self._off_dev, step, out=acts_lp)
+                sample_actions_dev(logits, self.seed, self._off_dev, step, out=acts_lp, avail=av)
             else:
-                sample_actions(logits, self.seed, self.offset, out=acts_lp)
+                sample_actions(logits, self.seed, self.offset, out=acts_lp, avail=av)
             self.offset += 1
             self.mb_values[step] = critic(self.mb_global_states[step], self.mb_global_vector[step]).reshape(E)
             # step + the next observations in one launch (MAPPO/trainer.py:229-286)

@@ -18,6 +18,10 @@
                     replay append, and one collector step against the host-driven loop
   --eval            device-resident evaluation: the greedy agent's mask, episode_results against the
                     read_state export, and one greedy evaluation against the host-driven loop
+  --avail           the valid-action mask: avail_actions per call (null, all-ones and all-zero masks)
+                    beside episode_results and the all-zero greedy_actions_masked, and one QMIX collect
+                    with the mask on and off; --avail-collect off: the collect alone, without
+                    the option (it runs on a build that predates it)
 
 Prints one JSON line per config with per-kernel HIP-event times and the
 algorithmic-bytes roofline of SURVEY.md §8(d).
@@ -868,6 +872,112 @@ def run_eval_bench(steps):
         env.close()
 
 
+def run_avail(steps, collect="both"):
+    """The valid-action mask ("Valid-action masks").  hipGraphs of G calls, five
+    interleaved repeats each.
+
+    1. ``avail_actions`` per call with no mask, an all-ones and an all-zero ``active``, 30 greedy steps
+       into the episodes of the README evaluation configuration (map1, A=5, P=100, T=1000, env e
+       seeded 10 + e) at 100 and 4,096 envs, beside the existing launch-bound small kernels on the
+       same box in the same run: ``episode_results`` and ``greedy_actions_masked`` with an all-zero
+       mask (its graph is [greedy_init, G calls], as in --eval).
+    2. ``QmixCollector.collect(graph=True)`` per env-step, L = 50, with ``avail`` on and off, a small
+       GRU agent on the actor vector (map1, A=5, P=20, 100 and 4,096 envs).  collect="off" times the
+       off case alone through the constructor without the argument.
+    """
+    import marl_gpu
+    import marl_gpu.qmix_rollout as Q
+    from marl_gpu.maps import grid_array, load_map, map_path
+    g1 = grid_array(load_map(map_path("map1.txt")))
+    dev = torch.device("cuda", 0)
+    G = 50
+    reps = max(2, steps // G)
+
+    def many(fn):
+        def f():
+            for _ in range(G):
+                fn()
+        return f
+
+    for E in (100, 4096) if collect == "both" else ():
+        A, P, T = 5, 100, 1000
+        env = marl_gpu.BatchedEnv(g1, E, A, P, T, seeds=[10 + e for e in range(E)], tracker="fresh")
+        env.reset()
+        env.greedy_init()
+        acts = torch.zeros((E, A), dtype=torch.uint8, device=dev)
+        ones = torch.ones(E, dtype=torch.uint8, device=dev)
+        zeros = torch.zeros(E, dtype=torch.uint8, device=dev)
+        for _ in range(30):
+            env.greedy_actions(out=acts)
+            env.step(acts, auto_reset=False, action_format="codes")
+        mask = torch.zeros((E, A, 15), dtype=torch.uint8, device=dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        res = (torch.zeros(E, dtype=torch.float64, device=dev), torch.zeros(E, **i32), torch.zeros(E, **i32))
+
+        def greedy_zero():
+            env.greedy_init()
+            for _ in range(G):
+                env.greedy_actions_masked(zeros, out=acts)
+
+        graphs = {"avail_null_us": _graph_of(many(lambda: env.avail_actions(out=mask))),
+                  "avail_all_ones_us": _graph_of(many(lambda: env.avail_actions(ones, out=mask))),
+                  "avail_all_zero_us": _graph_of(many(lambda: env.avail_actions(zeros, out=mask))),
+                  "episode_results_us": _graph_of(many(lambda: env.episode_results(out=res))),
+                  "greedy_masked_all_zero_us": _graph_of(greedy_zero)}
+        t = {k: [] for k in graphs}
+        for _ in range(5):
+            for k, g in graphs.items():
+                t[k].append(_replay_us(g, reps, G))
+        env.avail_actions(out=mask)
+        print(json.dumps({"config": "avail_actions", "envs": E, "agents": A, "packages": P, "graph_calls": G,
+                          "replays": reps, **t, "mask_bytes": E * A * 15,
+                          "masked_fraction": float((mask == 0).float().mean()),
+                          "note": "us per call; the greedy graph is [greedy_init, G calls], so its figure carries "
+                                  "1/G of one greedy_init"}), flush=True)
+        del graphs
+        env.close()
+
+    class Agent(torch.nn.Module):
+        def __init__(self, dv, hd=64):
+            super().__init__()
+            self.hd = hd
+            self.fc, self.rnn, self.out = torch.nn.Linear(dv, hd), torch.nn.GRUCell(hd, hd), torch.nn.Linear(hd, 15)
+
+        def init_hidden(self):
+            return self.fc.weight.new_zeros(1, self.hd)
+
+        def forward(self, so, vo, h):
+            h = self.rnn(torch.relu(self.fc(vo)), h)
+            return self.out(h), h
+
+    for E in (100, 4096):
+        A, P, T, L = 5, 20, 500, 50
+        modes = {"off": {}} if collect == "off" else {"off": {}, "on": {"avail": True}}
+        cols, envs = {}, []
+        torch.manual_seed(0)
+        agent = None
+        for name, kw in modes.items():
+            env = marl_gpu.BatchedEnv(g1, E, A, P, T, seed=42, tracker="fresh", shaping="qmix")
+            envs.append(env)
+            if agent is None:
+                agent = Agent(env.actor_vec_dim).to(dev)
+            cols[name] = Q.QmixCollector(env, L, seed=1, **kw)
+            cols[name].collect(agent, 0.2, graph=True)      # eager run + capture
+            cols[name].collect(agent, 0.2, graph=True)
+        n = max(2, steps // 10)
+        t = {name: [] for name in cols}
+        for _ in range(5):
+            for name, col in cols.items():
+                t[name].append(timed(lambda k: col.collect(agent, 0.2, graph=True), n) / L)
+        print(json.dumps({"config": "avail_qmix_collect", "envs": E, "agents": A, "packages": P, "episode_limit": L,
+                          "collects": n, **{f"collect_step_avail_{k}_us": v for k, v in t.items()},
+                          "note": "us per env-step of collect(graph=True): reset, observations, L x (agent forward, "
+                                  "selection, step_episode), and with avail on L + 1 avail_actions launches"}),
+              flush=True)
+        for env in envs:
+            env.close()
+
+
 def run_config1(seconds=5.0):
     """BASELINE.json configs[0]: map1, 5 agents, ONE env, a random agent driving the dict
     API (randomagent.py: np.random.choice over moves and ops per robot) -- plumbing, not a
@@ -907,8 +1017,14 @@ def main():
     ap.add_argument("--idq", action="store_true", help="the IDQ transition-collection measurements only")
     ap.add_argument("--qmix-cycle", action="store_true", help="the map-QMIX cycle-collection measurements only")
     ap.add_argument("--eval", action="store_true", help="the device-resident evaluation measurements only")
+    ap.add_argument("--avail", action="store_true", help="the valid-action mask measurements only")
+    ap.add_argument("--avail-collect", default="both", choices=["both", "off"],
+                    help="with --avail: off = the QMIX collect without the option alone")
     a = ap.parse_args()
     torch.cuda.set_device(0)
+    if a.avail:
+        run_avail(a.steps, a.avail_collect)
+        return
     if a.eval:
         run_eval_bench(a.steps)
         return
