@@ -2,6 +2,7 @@
 // shaping, device side:
 //   alt_emit_idq    convert_state              IDQ/networks.py:112-217 (qmix/networks.py:243-348 is the same code)
 //   alt_emit_qmix   convert_global_state_to_tensor           qmix/networks.py:350-468
+//   alt_emit_rows   both for one row of the engine builders' outputs (fast or general emission)
 //   idq_reward      reward_shaping                           IDQ/networks.py:228-349
 // One wave per state; per-cell scratch in the wave's LDS slice.
 #pragma once
@@ -235,6 +236,27 @@ __device__ inline void alt_emit_qmix(const uint8_t* grid, int H, int W, const Al
             default: return L.urg[m] >= 0.0f ? L.urg[m] : 0.0f;
         }
     });
+}
+
+// Row `row` of the engine builders' outputs (every agent's idq planes, the qmix state) from the
+// scratch alt_prepare filled: alt_emit_fast where the map, the state shape and the row addresses
+// allow float4 planes, else the general emission.
+template <class Trk>
+__device__ __forceinline__ void alt_emit_rows(const Trk& trk, const DevParams& p, const MapDesc& md, const AltLds& L,
+                                              int cell, int carry, size_t row, float* idq, float* qst, int oh,
+                                              int ow) {
+    const int A = p.A, H = md.H, W = md.W;
+    const uint8_t* grid = p.grids + md.grid_off;
+    float* idq_e = idq ? idq + row * A * 6 * H * W : nullptr;
+    float* qst_e = qst ? qst + row * 7 * oh * ow : nullptr;
+    const bool fast = (H * W) % 4 == 0 && oh == H && ow == W && (((uintptr_t)idq_e | (uintptr_t)qst_e) & 15) == 0;
+    if (fast) {
+        alt_bits(p.gridbits + md.bits_off, H * W, L);
+        alt_emit_fast(trk, H, W, L, cell, carry, A, idq_e, qst_e);
+        return;
+    }
+    if (idq) alt_emit_idq(trk, grid, H, W, L, cell, carry, 0, A, true, idq_e);
+    if (qst) alt_emit_qmix(grid, H, W, L, oh, ow, qst_e);
 }
 
 // What reward_shaping reads of the tracker from before the step, per agent:

@@ -1237,19 +1237,29 @@ int mdl_host_views_shaped_reward(MdlEngine* eng, const int32_t* prev_views, cons
 }
 
 // ---- IDQ / qmix featurizers and IDQ reward shaping ----
+// The engine builders' shared checks, in the order their callers see them: the qmix state shape, then for
+// envs [b, b + n) their same-shape run (`all`: mdl_alt_transition's full-batch wording) and the `lds` bytes
+// per wave.  Returns the waves per workgroup, 0 for n == 0 (nothing to launch), -1 after fail().
+static int alt_launch_shape(const MdlEngine* eng, const char* who, int b, int n, bool all, const float* qmix_state,
+                            int out_h, int out_w, size_t lds) {
+    if (qmix_state && (out_h < 1 || out_w < 1 || out_h > 4096 || out_w > 4096))
+        return fail("%s: bad state tensor shape (%d, %d)", who, out_h, out_w);
+    if (n == 0) return 0;
+    const int end = eng->shape_run_end[b];
+    if (end < b + n)
+        return all ? fail("%s: the envs mix map shapes (same-shape run ends at %d)", who, end)
+                   : fail("%s: envs [%d, %d) mix map shapes (same-shape run ends at %d)", who, b, b + n, end);
+    const int wpb = waves_per_block(lds);
+    return wpb < 1 ? fail("%s: needs %zu bytes of LDS per env", who, lds) : wpb;
+}
+
 int mdl_build_obs_alt(MdlEngine* eng, int32_t env_begin, int32_t n, float* idq_obs, float* qmix_state, int32_t out_h,
                       int32_t out_w, void* stream) {
     if (!eng) return fail("mdl_build_obs_alt: null engine");
     if (env_begin < 0 || n < 0 || env_begin + n > eng->p.E) return fail("mdl_build_obs_alt: env range out of bounds");
-    if (qmix_state && (out_h < 1 || out_w < 1 || out_h > 4096 || out_w > 4096))
-        return fail("mdl_build_obs_alt: bad state tensor shape (%d, %d)", out_h, out_w);
-    if (n == 0) return 0;
-    if (eng->shape_run_end[env_begin] < env_begin + n)
-        return fail("mdl_build_obs_alt: envs [%d, %d) mix map shapes (same-shape run ends at %d)", env_begin,
-                    env_begin + n, eng->shape_run_end[env_begin]);
     const size_t lds = mdl::alt_obs_lds(eng->p.P, eng->maxHW);
-    const int wpb = waves_per_block(lds);
-    if (wpb < 1) return fail("mdl_build_obs_alt: needs %zu bytes of LDS per env", lds);
+    const int wpb = alt_launch_shape(eng, "mdl_build_obs_alt", env_begin, n, false, qmix_state, out_h, out_w, lds);
+    if (wpb <= 0) return wpb;
     DeviceGuard dg(eng->device);
     HIPCHK(mdl::launch_alt_obs(eng->p, env_begin, n, idq_obs, qmix_state, out_h, out_w, wpb, lds,
                                (hipStream_t)stream));
@@ -1270,14 +1280,9 @@ int mdl_alt_transition(MdlEngine* eng, const uint8_t* actions, int32_t action_fo
     if (((uintptr_t)pre & 15) != 0) return fail("mdl_alt_transition: pre must be 16-byte aligned");
     if (actions && action_format != MDL_ACTION_TRAINER_INT && action_format != MDL_ACTION_CODES)
         return fail("mdl_alt_transition: unknown action_format %d", action_format);
-    if (qmix_state && (out_h < 1 || out_w < 1 || out_h > 4096 || out_w > 4096))
-        return fail("mdl_alt_transition: bad state tensor shape (%d, %d)", out_h, out_w);
-    const int E = eng->p.E;
-    if (eng->shape_run_end[0] < E)
-        return fail("mdl_alt_transition: the envs mix map shapes (same-shape run ends at %d)", eng->shape_run_end[0]);
     const size_t lds = mdl::alt_obs_lds(eng->p.P, eng->maxHW);
-    const int wpb = waves_per_block(lds);
-    if (wpb < 1) return fail("mdl_alt_transition: needs %zu bytes of LDS per env", lds);
+    const int wpb = alt_launch_shape(eng, "mdl_alt_transition", 0, eng->p.E, true, qmix_state, out_h, out_w, lds);
+    if (wpb <= 0) return wpb;
     DeviceGuard dg(eng->device);
     HIPCHK(mdl::launch_alt_transition(eng->p, actions, action_format, ops_are_ints, row_mask, pre,
                                       actions ? r_idq : nullptr, idq_obs, qmix_state, out_h, out_w, wpb, lds,
@@ -1290,15 +1295,9 @@ int mdl_cycle_begin(MdlEngine* eng, uint8_t* done, uint8_t* completed, double* c
                     void* stream) {
     if (!eng || !done) return fail("mdl_cycle_begin: null argument");
     if (!eng->seeded) return fail("mdl_cycle_begin: engine not seeded (call mdl_seed first)");
-    if (qmix_state && (out_h < 1 || out_w < 1 || out_h > 4096 || out_w > 4096))
-        return fail("mdl_cycle_begin: bad state tensor shape (%d, %d)", out_h, out_w);
-    const int E = eng->p.E;
-    if (eng->shape_run_end[0] < E)
-        return fail("mdl_cycle_begin: envs [%d, %d) mix map shapes (same-shape run ends at %d)", 0, E,
-                    eng->shape_run_end[0]);
     const size_t lds = mdl::cycle_begin_lds(eng->p.P, eng->maxHW);
-    const int wpb = waves_per_block(lds);
-    if (wpb < 1) return fail("mdl_cycle_begin: needs %zu bytes of LDS per env", lds);
+    const int wpb = alt_launch_shape(eng, "mdl_cycle_begin", 0, eng->p.E, false, qmix_state, out_h, out_w, lds);
+    if (wpb <= 0) return wpb;
     DeviceGuard dg(eng->device);
     HIPCHK(mdl::launch_cycle_begin(eng->p, done, completed, completed_return, completed_steps, idq_obs, qmix_state,
                                    out_h, out_w, wpb, lds, (hipStream_t)stream));

@@ -1298,6 +1298,33 @@ __device__ inline ObsLdsPre obs_pre_carve(unsigned char* base, int P) {
     return S;
 }
 
+// Env e's package table and tracker into the wave's slots (entry data and order keys only with a
+// stale tracker), then the wave's sync: what every builder below reads by id.  P and the lane are the
+// caller's own values: read again here, k_obs compiles to other code (profiles/builder_shared/).
+template <bool STALE>
+__device__ __forceinline__ void stage_tracker(const DevParams& p, int e, int P, int lane, const ObsLdsPre& S) {
+    for (int j = lane; j < P; j += WAVE) {
+        const size_t g = (size_t)e * P + j;
+        const uint64_t d = p.pkg[g];
+        const uint32_t f = p.pstate[g];
+        S.pk[j] = d;
+        S.ps[j] = (uint8_t)(f & PS_FLAGS);
+        if (STALE) {
+            const bool sv = (f & PS_SURVIVOR) != 0;
+            S.td[j] = sv ? p.trk[g] : d;
+            S.tq[j] = sv ? f >> PS_RANK_SHIFT : ORD_EPISODE + (uint32_t)j;
+        }
+    }
+    wave_sync();
+}
+
+// The staged slots as the engine's tracker: stale (its own entry data and order keys) or fresh
+template <bool STALE>
+__device__ __forceinline__ auto staged_tracker(const ObsLdsPre& S, int P) {
+    if constexpr (STALE) return TrkStale{S.ps, S.td, S.tq, P};
+    else return TrkFresh{S.pk, S.ps, P};
+}
+
 template <bool STALE>
 __global__ __launch_bounds__(256) void k_obs(DevParams p, int env_begin, int n, float* __restrict__ amap,
                                              float* __restrict__ avec, float* __restrict__ cmap,
@@ -1334,19 +1361,7 @@ __global__ __launch_bounds__(256) void k_obs(DevParams p, int env_begin, int n, 
     const uint32_t rv = act ? p.rob[(size_t)e * A + lane] : 0u;
     const int cell = rob_cell(rv);
     const int carry = rob_carry(rv);
-    for (int j = lane; j < P; j += WAVE) {
-        const size_t g = (size_t)e * P + j;
-        const uint64_t d = p.pkg[g];
-        const uint32_t f = p.pstate[g];
-        S.pk[j] = d;
-        S.ps[j] = (uint8_t)(f & PS_FLAGS);
-        if (STALE) {
-            const bool sv = (f & PS_SURVIVOR) != 0;
-            S.td[j] = sv ? p.trk[g] : d;
-            S.tq[j] = sv ? f >> PS_RANK_SHIFT : ORD_EPISODE + (uint32_t)j;
-        }
-    }
-    wave_sync();
+    stage_tracker<STALE>(p, e, P, lane, S);
     auto run = [&](const auto& trk) {
         feat_prepare(trk, c, L, cell, carry);
         const size_t le = (size_t)w;
@@ -1377,13 +1392,7 @@ __global__ __launch_bounds__(256) void k_obs(DevParams p, int env_begin, int n, 
             emit_critic_vec(trk, c, L, cvec + le * (size_t)Dg);
         }
     };
-    if (STALE) {
-        TrkStale trk{S.ps, S.td, S.tq, P};
-        run(trk);
-    } else {
-        TrkFresh trk{S.pk, S.ps, P};
-        run(trk);
-    }
+    run(staged_tracker<STALE>(S, P));
 }
 
 // ------------------------------------------------------ dict views (helpers)
@@ -1433,27 +1442,11 @@ __device__ inline TrkView load_view_rows(const int32_t* rec, int A, int ns, View
 
 __device__ inline TrkView load_view(const int32_t* rec, ViewLdsPre& V, int& t, int& A, int& map, int& cell,
                                     int& carry) {
-    const int lane = lane_id();
     t = rec[0];
     A = rec[1];
     const int ns = rec[2];
     map = rec[3];
-    const int32_t* rb = rec + 4;
-    cell = 0;
-    carry = 0;
-    if (lane < A) {
-        cell = rb[3 * lane] | (rb[3 * lane + 1] << 8);
-        carry = rb[3 * lane + 2];
-    }
-    const int32_t* sl = rb + 3 * A;
-    for (int j = lane; j < ns; j += WAVE) {
-        const int32_t* s = sl + 8 * j;
-        V.ids[j] = s[0];
-        V.flag[j] = (uint8_t)(1 | (s[1] == ST_IN_TRANSIT ? 2 : 0));
-        V.pk[j] = pk_make(s[2] | (s[3] << 8), s[4] | (s[5] << 8), s[6], s[7]);
-    }
-    wave_sync();
-    return TrkView{V.ids, V.flag, V.pk, ns};
+    return load_view_rows(rec, A, ns, V, cell, carry);
 }
 
 // view record `rec`, agent index `a`, outputs row w
@@ -1602,40 +1595,12 @@ __global__ __launch_bounds__(256) void k_alt_obs(DevParams p, int env_begin, int
     const uint32_t rv = act ? p.rob[(size_t)e * A + lane] : 0u;
     const int cell = rob_cell(rv), carry = rob_carry(rv);
     const int t = p.es[e].t;
-    for (int j = lane; j < P; j += WAVE) {
-        const size_t g = (size_t)e * P + j;
-        const uint64_t d = p.pkg[g];
-        const uint32_t f = p.pstate[g];
-        S.pk[j] = d;
-        S.ps[j] = (uint8_t)(f & PS_FLAGS);
-        if (STALE) {
-            const bool sv = (f & PS_SURVIVOR) != 0;
-            S.td[j] = sv ? p.trk[g] : d;
-            S.tq[j] = sv ? f >> PS_RANK_SHIFT : ORD_EPISODE + (uint32_t)j;
-        }
-    }
-    wave_sync();
-    const uint8_t* grid = p.grids + md.grid_off;
-    float* idq_e = idq ? idq + (size_t)w * A * 6 * H * W : nullptr;
-    float* qst_e = qst ? qst + (size_t)w * 7 * oh * ow : nullptr;
-    const bool fast = (H * W) % 4 == 0 && oh == H && ow == W && (((uintptr_t)idq_e | (uintptr_t)qst_e) & 15) == 0;
+    stage_tracker<STALE>(p, e, P, lane, S);
     auto run = [&](const auto& trk) {
         alt_prepare(trk, H * W, W, A, t, cell, carry, L);
-        if (fast) {
-            alt_bits(p.gridbits + md.bits_off, H * W, L);
-            alt_emit_fast(trk, H, W, L, cell, carry, A, idq_e, qst_e);
-            return;
-        }
-        if (idq) alt_emit_idq(trk, grid, H, W, L, cell, carry, 0, A, true, idq_e);
-        if (qst) alt_emit_qmix(grid, H, W, L, oh, ow, qst_e);
+        alt_emit_rows(trk, p, md, L, cell, carry, (size_t)w, idq, qst, oh, ow);
     };
-    if (STALE) {
-        TrkStale trk{S.ps, S.td, S.tq, P};
-        run(trk);
-    } else {
-        TrkFresh trk{S.pk, S.ps, P};
-        run(trk);
-    }
+    run(staged_tracker<STALE>(S, P));
 }
 
 // mdl_alt_transition: one IDQ transition's device side for the envs `mask` marks, after their step
@@ -1676,23 +1641,7 @@ __global__ __launch_bounds__(256) void k_alt_transition(DevParams p, const uint8
         const IdqTrkFacts f{(q.flags & ALT_PRE_AVAIL) != 0, (q.flags & ALT_PRE_TRACKED) != 0, q.target, q.deadline};
         r_idq[ra] = idq_reward_facts(rob_cell(q.rob), rob_carry(q.rob), cell, carry, ops_are_ints ? op : -1, t, f);
     }
-    for (int j = lane; j < P; j += WAVE) {   // the package table and tracker, as k_alt_obs loads them
-        const size_t g = (size_t)e * P + j;
-        const uint64_t d = p.pkg[g];
-        const uint32_t f = p.pstate[g];
-        S.pk[j] = d;
-        S.ps[j] = (uint8_t)(f & PS_FLAGS);
-        if (STALE) {
-            const bool sv = (f & PS_SURVIVOR) != 0;
-            S.td[j] = sv ? p.trk[g] : d;
-            S.tq[j] = sv ? f >> PS_RANK_SHIFT : ORD_EPISODE + (uint32_t)j;
-        }
-    }
-    wave_sync();
-    const uint8_t* grid = p.grids + md.grid_off;
-    float* idq_e = idq ? idq + (size_t)e * A * 6 * H * W : nullptr;
-    float* qst_e = qst ? qst + (size_t)e * 7 * oh * ow : nullptr;
-    const bool fast = (H * W) % 4 == 0 && oh == H && ow == W && (((uintptr_t)idq_e | (uintptr_t)qst_e) & 15) == 0;
+    stage_tracker<STALE>(p, e, P, lane, S);
     auto run = [&](const auto& trk) {
         alt_prepare(trk, H * W, W, A, t, cell, carry, L);
         if (act) {   // the record of this state: what the next step's reward reads
@@ -1707,21 +1656,9 @@ __global__ __launch_bounds__(256) void k_alt_transition(DevParams p, const uint8
             pre[ra] = n;
         }
         if (lane == 0) pre_t[e] = t;   // the record's time step (the reward itself reads only `avail`, taken at it)
-        if (fast) {
-            alt_bits(p.gridbits + md.bits_off, H * W, L);
-            alt_emit_fast(trk, H, W, L, cell, carry, A, idq_e, qst_e);
-            return;
-        }
-        if (idq) alt_emit_idq(trk, grid, H, W, L, cell, carry, 0, A, true, idq_e);
-        if (qst) alt_emit_qmix(grid, H, W, L, oh, ow, qst_e);
+        alt_emit_rows(trk, p, md, L, cell, carry, (size_t)e, idq, qst, oh, ow);
     };
-    if (STALE) {
-        TrkStale trk{S.ps, S.td, S.tq, P};
-        run(trk);
-    } else {
-        TrkFresh trk{S.pk, S.ps, P};
-        run(trk);
-    }
+    run(staged_tracker<STALE>(S, P));
 }
 
 // mdl_cycle_begin: the lazy reset that opens a time step of the map-QMIX cycle
@@ -1808,27 +1745,12 @@ __global__ __launch_bounds__(256) void k_cycle_begin(DevParams p, uint8_t* __res
         done[e] = 0;
     }
     wave_sync();
-    const uint8_t* grid = p.grids + md.grid_off;
-    float* idq_e = idq ? idq + (size_t)e * A * 6 * H * W : nullptr;
-    float* qst_e = qst ? qst + (size_t)e * 7 * oh * ow : nullptr;
-    const bool fast = (H * W) % 4 == 0 && oh == H && ow == W && (((uintptr_t)idq_e | (uintptr_t)qst_e) & 15) == 0;
     auto run = [&](const auto& trk) {
         alt_prepare(trk, H * W, W, A, 0, cell, 0, AL);
-        if (fast) {
-            alt_bits(p.gridbits + md.bits_off, H * W, AL);
-            alt_emit_fast(trk, H, W, AL, cell, 0, A, idq_e, qst_e);
-            return;
-        }
-        if (idq) alt_emit_idq(trk, grid, H, W, AL, cell, 0, 0, A, true, idq_e);
-        if (qst) alt_emit_qmix(grid, H, W, AL, oh, ow, qst_e);
+        alt_emit_rows(trk, p, md, AL, cell, 0, (size_t)e, idq, qst, oh, ow);
     };
-    if (STALE) {
-        TrkStale trk{L.pst, L.pk, (const uint32_t*)L.scratch, P};
-        run(trk);
-    } else {
-        TrkFresh trk{L.pk, L.pst, P};
-        run(trk);
-    }
+    // the reset scratch as the staged slots (above): L.pk is the table and the entry data alike
+    run(staged_tracker<STALE>(ObsLdsPre{L.pk, L.pk, (uint32_t*)L.scratch, L.pst}, P));
 }
 
 // The same builders on packed dict views (one agent index per view).
@@ -2113,6 +2035,12 @@ __global__ __launch_bounds__(64) void k_publish(int32_t* seq, int32_t value) {
 // ---------------------------------------------------------------- launchers
 static int blocks_for(int n, int wpb) { return (n + wpb - 1) / wpb; }
 
+// f(std::integral_constant<int, V>{}) for the V of Vs... that equals v
+template <int... Vs, class F>
+static void with_int(int v, F&& f) {
+    (void)((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
+}
+
 hipError_t launch_publish(int32_t* seq, int32_t value, hipStream_t s) {
     hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, s, seq, value);
     return hipGetLastError();
@@ -2138,19 +2066,11 @@ hipError_t launch_seed(const DevParams& p, const uint32_t* seeds, int wpb, size_
     return hipGetLastError();
 }
 
-template <int NCH>
-static void launch_reset_t(const DevParams& p, const int* ids, int n, int wpb, size_t lds, hipStream_t s) {
-    hipLaunchKernelGGL(k_reset<NCH>, dim3(blocks_for(n, wpb)), dim3(256), lds * wpb, s, p, ids, n, wpb, (int)lds);
-}
-
 hipError_t launch_reset(const DevParams& p, const int* ids, int n, int wpb, size_t lds, hipStream_t s) {
-    switch (nch_for(p.P)) {
-        case 1: launch_reset_t<1>(p, ids, n, wpb, lds, s); break;
-        case 2: launch_reset_t<2>(p, ids, n, wpb, lds, s); break;
-        case 4: launch_reset_t<4>(p, ids, n, wpb, lds, s); break;
-        case 8: launch_reset_t<8>(p, ids, n, wpb, lds, s); break;
-        default: launch_reset_t<16>(p, ids, n, wpb, lds, s); break;
-    }
+    with_int<1, 2, 4, 8, 16>(nch_for(p.P), [&](auto nch) {
+        hipLaunchKernelGGL(k_reset<decltype(nch)::value>, dim3(blocks_for(n, wpb)), dim3(256), lds * wpb, s, p, ids,
+                           n, wpb, (int)lds);
+    });
     return hipGetLastError();
 }
 
@@ -2178,12 +2098,6 @@ size_t step_halves_lds(int P) {
 // ---- the step launches: one kernel selection (select_step), one argument path (step_launch) ----
 // STEP_PLAIN: k_step, k_step_halves or k_step_rows by envs per wave (1, 2, 4); the others: one wave per env
 enum StepVariant { STEP_PLAIN, STEP_FUSED, STEP_OBS, STEP_MAIL, STEP_EPISODE };
-
-// f(std::integral_constant<int, V>{}) for the V of Vs... that equals v
-template <int... Vs, class F>
-static void with_int(int v, F&& f) {
-    (void)((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
-}
 
 // The step kernel a launch of variant V over `envs_per_wave` envs per wavefront runs: calls
 // f(kernel, fmt, args...) with the instantiation and its symbol as rocprof names it -- a printf
@@ -2368,12 +2282,10 @@ size_t views_alt_lds(int NSmax, int HW) { return view_pre_bytes(NSmax) + alt_lds
 
 hipError_t launch_alt_obs(const DevParams& p, int env_begin, int n, float* idq, float* qst, int oh, int ow, int wpb,
                           size_t lds, hipStream_t s) {
-    if (p.stale)
-        hipLaunchKernelGGL(k_alt_obs<true>, dim3(blocks_for(n, wpb)), dim3(256), lds * wpb, s, p, env_begin, n, idq,
-                           qst, oh, ow, wpb, (int)lds);
-    else
-        hipLaunchKernelGGL(k_alt_obs<false>, dim3(blocks_for(n, wpb)), dim3(256), lds * wpb, s, p, env_begin, n, idq,
-                           qst, oh, ow, wpb, (int)lds);
+    with_int<0, 1>(p.stale != 0, [&](auto st) {
+        hipLaunchKernelGGL(k_alt_obs<decltype(st)::value != 0>, dim3(blocks_for(n, wpb)), dim3(256), lds * wpb, s, p,
+                           env_begin, n, idq, qst, oh, ow, wpb, (int)lds);
+    });
     return hipGetLastError();
 }
 
@@ -2384,12 +2296,11 @@ hipError_t launch_alt_transition(const DevParams& p, const uint8_t* acts, int fm
                                  int wpb, size_t lds, hipStream_t s) {
     AltPre* pr = (AltPre*)pre;
     int32_t* pt = (int32_t*)((char*)pre + alt_pre_t_off(p.E, p.A));
-    if (p.stale)
-        hipLaunchKernelGGL(k_alt_transition<true>, dim3(blocks_for(p.E, wpb)), dim3(256), lds * wpb, s, p, acts, fmt,
-                           ops_are_ints, mask, pr, pt, r_idq, idq, qst, oh, ow, wpb, (int)lds);
-    else
-        hipLaunchKernelGGL(k_alt_transition<false>, dim3(blocks_for(p.E, wpb)), dim3(256), lds * wpb, s, p, acts, fmt,
-                           ops_are_ints, mask, pr, pt, r_idq, idq, qst, oh, ow, wpb, (int)lds);
+    with_int<0, 1>(p.stale != 0, [&](auto st) {
+        hipLaunchKernelGGL(k_alt_transition<decltype(st)::value != 0>, dim3(blocks_for(p.E, wpb)), dim3(256),
+                           lds * wpb, s, p, acts, fmt, ops_are_ints, mask, pr, pt, r_idq, idq, qst, oh, ow, wpb,
+                           (int)lds);
+    });
     return hipGetLastError();
 }
 
@@ -2400,13 +2311,10 @@ hipError_t launch_cycle_begin(const DevParams& p, uint8_t* done, uint8_t* comple
                               hipStream_t s) {
     const dim3 g(blocks_for(p.E, wpb)), b(256);
     with_int<1, 2, 4, 8, 16>(nch_for(p.P), [&](auto nch) {   // the package chunks, as launch_reset picks them
-        constexpr int NCH = decltype(nch)::value;
-        if (p.stale)
-            hipLaunchKernelGGL((k_cycle_begin<true, NCH>), g, b, lds * wpb, s, p, done, completed, c_return, c_steps,
-                               idq, qst, oh, ow, wpb, (int)lds);
-        else
-            hipLaunchKernelGGL((k_cycle_begin<false, NCH>), g, b, lds * wpb, s, p, done, completed, c_return, c_steps,
-                               idq, qst, oh, ow, wpb, (int)lds);
+        with_int<0, 1>(p.stale != 0, [&](auto st) {
+            hipLaunchKernelGGL((k_cycle_begin<decltype(st)::value != 0, decltype(nch)::value>), g, b, lds * wpb, s, p,
+                               done, completed, c_return, c_steps, idq, qst, oh, ow, wpb, (int)lds);
+        });
     });
     return hipGetLastError();
 }
@@ -2430,28 +2338,19 @@ hipError_t launch_views_idq_reward(const int32_t* prev, const int64_t* prev_offs
 
 hipError_t launch_obs(const DevParams& p, int env_begin, int n, float* amap, float* avec, float* cmap, float* cvec,
                       int wpb, size_t lds, hipStream_t s, int rank_lds, const uint8_t* mask) {
-    if (p.obs_small) {
-        const dim3 g(blocks_for(n, wpb)), b(256);
-        const size_t dyn = (size_t)rank_lds + lds * wpb;
-#define MDL_OBS_SMALL(ST, RL) \
-    hipLaunchKernelGGL((k_obs_small<ST, RL>), g, b, dyn, s, p, env_begin, n, amap, avec, cmap, cvec, wpb, (int)lds, rank_lds, \
-                       mask)
-        if (p.stale) {
-            if (rank_lds > 0) MDL_OBS_SMALL(true, true);
-            else MDL_OBS_SMALL(true, false);
-        } else {
-            if (rank_lds > 0) MDL_OBS_SMALL(false, true);
-            else MDL_OBS_SMALL(false, false);
+    const dim3 g(blocks_for(n, wpb)), b(256);
+    with_int<0, 1>(p.stale != 0, [&](auto st) {
+        constexpr bool ST = decltype(st)::value != 0;
+        if (!p.obs_small) {
+            hipLaunchKernelGGL(k_obs<ST>, g, b, lds * wpb, s, p, env_begin, n, amap, avec, cmap, cvec, wpb, (int)lds,
+                               mask);
+            return;
         }
-#undef MDL_OBS_SMALL
-        return hipGetLastError();
-    }
-    if (p.stale)
-        hipLaunchKernelGGL(k_obs<true>, dim3(blocks_for(n, wpb)), dim3(256), lds * wpb, s, p, env_begin, n, amap,
-                           avec, cmap, cvec, wpb, (int)lds, mask);
-    else
-        hipLaunchKernelGGL(k_obs<false>, dim3(blocks_for(n, wpb)), dim3(256), lds * wpb, s, p, env_begin, n, amap,
-                           avec, cmap, cvec, wpb, (int)lds, mask);
+        with_int<0, 1>(rank_lds > 0, [&](auto rl) {   // the rank table staged in LDS, ahead of the waves' slices
+            hipLaunchKernelGGL((k_obs_small<ST, decltype(rl)::value != 0>), g, b, (size_t)rank_lds + lds * wpb, s, p,
+                               env_begin, n, amap, avec, cmap, cvec, wpb, (int)lds, rank_lds, mask);
+        });
+    });
     return hipGetLastError();
 }
 
@@ -2464,37 +2363,34 @@ hipError_t launch_views_features(const DevParams& p, const int32_t* views, const
     return hipGetLastError();
 }
 
+// f(CAP, record) with the view record copied into the smallest ViewInline<CAP> that holds it
+template <class F>
+static void with_view_inline(const int32_t* rec, int words, F&& f) {
+    with_int<VIEW_INLINE_SMALL, VIEW_INLINE_WORDS>(words <= VIEW_INLINE_SMALL ? VIEW_INLINE_SMALL : VIEW_INLINE_WORDS,
+                                                   [&](auto cap) {
+        ViewInline<decltype(cap)::value> r;
+        std::memcpy(r.w, rec, 4 * (size_t)words);
+        f(cap, r);
+    });
+}
+
 hipError_t launch_view_features_inline(const DevParams& p, const int32_t* rec, int words, int a, int T, int MO,
                                       int MP, int MR, int MPs, int MPc, int MPsc, int NSmax, int HW, float* obs,
                                       float* vec, float* gmap, float* gvec, size_t lds, hipStream_t s,
                                       const Publish& pb) {
-    if (words <= VIEW_INLINE_SMALL) {
-        ViewInline<VIEW_INLINE_SMALL> r;
-        std::memcpy(r.w, rec, 4 * (size_t)words);
-        hipLaunchKernelGGL(k_view_features_inl<VIEW_INLINE_SMALL>, dim3(1), dim3(64), lds, s, p, a, T, MO, MP, MR,
+    with_view_inline(rec, words, [&](auto cap, const auto& r) {
+        hipLaunchKernelGGL(k_view_features_inl<decltype(cap)::value>, dim3(1), dim3(64), lds, s, p, a, T, MO, MP, MR,
                            MPs, MPc, MPsc, NSmax, obs, vec, gmap, gvec, HW, pb, r);
-    } else {
-        ViewInline<VIEW_INLINE_WORDS> r;
-        std::memcpy(r.w, rec, 4 * (size_t)words);
-        hipLaunchKernelGGL(k_view_features_inl<VIEW_INLINE_WORDS>, dim3(1), dim3(64), lds, s, p, a, T, MO, MP, MR,
-                           MPs, MPc, MPsc, NSmax, obs, vec, gmap, gvec, HW, pb, r);
-    }
+    });
     return hipGetLastError();
 }
 
 hipError_t launch_view_shaped_inline(const int32_t* rec, int words, int co, int ao, double g, const ShapingConsts& C,
                                      int NSmax, size_t lds, hipStream_t s, const Publish& pb) {
-    if (words <= VIEW_INLINE_SMALL) {
-        ViewInline<VIEW_INLINE_SMALL> r;
-        std::memcpy(r.w, rec, 4 * (size_t)words);
-        hipLaunchKernelGGL(k_view_shaped_inl<VIEW_INLINE_SMALL>, dim3(1), dim3(64), lds, s, g, C, co, ao, NSmax, pb,
-                           r);
-    } else {
-        ViewInline<VIEW_INLINE_WORDS> r;
-        std::memcpy(r.w, rec, 4 * (size_t)words);
-        hipLaunchKernelGGL(k_view_shaped_inl<VIEW_INLINE_WORDS>, dim3(1), dim3(64), lds, s, g, C, co, ao, NSmax, pb,
-                           r);
-    }
+    with_view_inline(rec, words, [&](auto cap, const auto& r) {
+        hipLaunchKernelGGL(k_view_shaped_inl<decltype(cap)::value>, dim3(1), dim3(64), lds, s, g, C, co, ao, NSmax,
+                           pb, r);
+    });
     return hipGetLastError();
 }
 

@@ -45,10 +45,20 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32
 // e_i = exp(l_i - max) and S = sum e_i (sequential fp32 sums); log_prob =
 // (l_a - max) - log(S).  Rows whose logits are all -inf get action 0, -inf.
 // off_dev (graph-capturable form): the offset is *off_dev + off_lo|off_hi<<32.
-__global__ __launch_bounds__(256) void k_sample(const float* __restrict__ logits, int64_t n_rows, int n_act,
-                                                uint32_t k0, uint32_t k1, uint32_t off_lo, uint32_t off_hi,
-                                                const uint64_t* __restrict__ off_dev, uint8_t* __restrict__ actions,
-                                                float* __restrict__ log_probs) {
+//
+// AVAIL (k_sample_avail): the softmax restricted to the row's available actions (avail uint8
+// [n_rows][n_act], non-zero = available): the same Philox block, the same sequential fp32 sums and
+// the same inverse CDF, with every unavailable action left out of the maximum, of S and of the
+// running sum, so its probability is exactly 0 and it is never returned; log_prob = (l_a - max) -
+// log(S) over the available actions.  With every action available each operation is k_sample's,
+// in its order: the same bits.  A row with no available action gets action 0, a row whose
+// available logits are all -inf its first available action (k_sample's 0 when all are), both
+// with log_prob -inf.
+template <bool AVAIL>
+__device__ __forceinline__ void sample_row(const float* __restrict__ logits, const uint8_t* __restrict__ avail,
+                                           int64_t n_rows, int n_act, uint32_t k0, uint32_t k1, uint32_t off_lo,
+                                           uint32_t off_hi, const uint64_t* __restrict__ off_dev,
+                                           uint8_t* __restrict__ actions, float* __restrict__ log_probs) {
     const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (row >= n_rows) return;
     if (off_dev) {
@@ -57,72 +67,47 @@ __global__ __launch_bounds__(256) void k_sample(const float* __restrict__ logits
         off_hi = (uint32_t)(o >> 32);
     }
     const float* l = logits + row * n_act;
+    const uint8_t* av = AVAIL ? avail + row * n_act : nullptr;
     float m = -INFINITY;
-    for (int i = 0; i < n_act; i++) m = fmaxf(m, l[i]);
+    for (int i = 0; i < n_act; i++)
+        if (!AVAIL || av[i]) m = fmaxf(m, l[i]);
     float S = 0.0f;
-    for (int i = 0; i < n_act; i++) S = S + expf(l[i] - m);
+    for (int i = 0; i < n_act; i++)
+        if (!AVAIL || av[i]) S = S + expf(l[i] - m);
     uint32_t c[4] = {off_lo, off_hi, (uint32_t)row, (uint32_t)(row >> 32)};
     philox4x32_10(c, k0, k1);
     const float u = (float)(c[0] >> 8) * 0x1p-24f;
     const float target = u * S;
-    int a = -1, last = 0;
+    // without a mask action 0 is the first available one, and the fallback of a row with no weight
+    int a = -1, last = AVAIL ? -1 : 0, first_av = AVAIL ? -1 : 0;
     float cum = 0.0f;
     for (int i = 0; i < n_act; i++) {
-        const float ei = expf(l[i] - m);
-        cum = cum + ei;
-        if (ei > 0.0f) last = i;
-        if (a < 0 && target < cum) a = i;
-    }
-    if (a < 0) a = last;  // u*S rounded up to the full sum
-    actions[row] = (uint8_t)a;
-    if (log_probs) log_probs[row] = (m == -INFINITY) ? -INFINITY : (l[a] - m) - logf(S);
-}
-
-// k_sample over the softmax restricted to the row's available actions (avail uint8 [n_rows][n_act],
-// non-zero = available): the same Philox block, the same sequential fp32 sums and the same inverse
-// CDF, with every unavailable action left out of the maximum, of S and of the running sum, so its
-// probability is exactly 0 and it is never returned; log_prob = (l_a - max) - log(S) over the
-// available actions.  With every action available each operation is k_sample's, in its order: the
-// same bits.  A row with no available action gets action 0, a row whose available logits are all
-// -inf its first available action (k_sample's 0 when all are), both with log_prob -inf.
-__global__ __launch_bounds__(256) void k_sample_avail(const float* __restrict__ logits,
-                                                      const uint8_t* __restrict__ avail, int64_t n_rows, int n_act,
-                                                      uint32_t k0, uint32_t k1, uint32_t off_lo, uint32_t off_hi,
-                                                      const uint64_t* __restrict__ off_dev,
-                                                      uint8_t* __restrict__ actions, float* __restrict__ log_probs) {
-    const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (row >= n_rows) return;
-    if (off_dev) {
-        const uint64_t o = *off_dev + ((uint64_t)off_hi << 32 | off_lo);
-        off_lo = (uint32_t)o;
-        off_hi = (uint32_t)(o >> 32);
-    }
-    const float* l = logits + row * n_act;
-    const uint8_t* av = avail + row * n_act;
-    float m = -INFINITY;
-    for (int i = 0; i < n_act; i++)
-        if (av[i]) m = fmaxf(m, l[i]);
-    float S = 0.0f;
-    for (int i = 0; i < n_act; i++)
-        if (av[i]) S = S + expf(l[i] - m);
-    uint32_t c[4] = {off_lo, off_hi, (uint32_t)row, (uint32_t)(row >> 32)};
-    philox4x32_10(c, k0, k1);
-    const float u = (float)(c[0] >> 8) * 0x1p-24f;
-    const float target = u * S;
-    int a = -1, last = -1, first_av = -1;
-    float cum = 0.0f;
-    for (int i = 0; i < n_act; i++) {
-        if (!av[i]) continue;
+        if (AVAIL && !av[i]) continue;
         const float ei = expf(l[i] - m);
         cum = cum + ei;
         if (first_av < 0) first_av = i;
         if (ei > 0.0f) last = i;
         if (a < 0 && target < cum) a = i;
     }
-    // u*S rounded up to the full sum: the last action with weight, as k_sample
+    // u*S rounded up to the full sum: the last action with weight
     if (a < 0) a = last >= 0 ? last : (first_av >= 0 ? first_av : 0);
     actions[row] = (uint8_t)a;
     if (log_probs) log_probs[row] = (m == -INFINITY) ? -INFINITY : (l[a] - m) - logf(S);
+}
+
+__global__ __launch_bounds__(256) void k_sample(const float* __restrict__ logits, int64_t n_rows, int n_act,
+                                                uint32_t k0, uint32_t k1, uint32_t off_lo, uint32_t off_hi,
+                                                const uint64_t* __restrict__ off_dev, uint8_t* __restrict__ actions,
+                                                float* __restrict__ log_probs) {
+    sample_row<false>(logits, nullptr, n_rows, n_act, k0, k1, off_lo, off_hi, off_dev, actions, log_probs);
+}
+
+__global__ __launch_bounds__(256) void k_sample_avail(const float* __restrict__ logits,
+                                                      const uint8_t* __restrict__ avail, int64_t n_rows, int n_act,
+                                                      uint32_t k0, uint32_t k1, uint32_t off_lo, uint32_t off_hi,
+                                                      const uint64_t* __restrict__ off_dev,
+                                                      uint8_t* __restrict__ actions, float* __restrict__ log_probs) {
+    sample_row<true>(logits, avail, n_rows, n_act, k0, k1, off_lo, off_hi, off_dev, actions, log_probs);
 }
 
 // One env per thread, t = T-1 .. 0 (MAPPO/trainer.py:266-276):
@@ -380,19 +365,30 @@ int rfail(const char* msg, hipError_t e = hipSuccess) {
 
 extern "C" {
 
+static int rfail_in(const char* what, const char* msg, hipError_t e = hipSuccess) {
+    char buf[96];
+    snprintf(buf, sizeof buf, "%s: %s", what, msg);
+    return rfail(buf, e);
+}
+
+// The row kernels' shared argument check (`in`: the logits / Q-values): -1 after the error is set,
+// 0 for an empty batch, else the launch's block count.
+static int64_t row_blocks(const char* what, const void* in, const void* actions, int64_t n_rows, int32_t n_actions) {
+    if (!in || !actions) return rfail_in(what, "null argument");
+    if (n_rows < 0 || n_actions < 1 || n_actions > 256) return rfail_in(what, "bad sizes");
+    return (n_rows + 255) / 256;
+}
+
+// ... and their shared end: the launch's status
+static int launched(const char* what) {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : rfail_in(what, "launch failed", e);
+}
+
 static int sample(const char* what, const float* logits, const uint8_t* avail, int64_t n_rows, int32_t n_actions, uint64_t seed,
                   uint64_t offset, const uint64_t* offset_dev, uint8_t* actions, float* log_probs, void* stream) {
-    char msg[96];
-    if (!logits || !actions) {
-        snprintf(msg, sizeof msg, "%s: null argument", what);
-        return rfail(msg);
-    }
-    if (n_rows < 0 || n_actions < 1 || n_actions > 256) {
-        snprintf(msg, sizeof msg, "%s: bad sizes", what);
-        return rfail(msg);
-    }
-    if (n_rows == 0) return 0;
-    const int64_t blocks = (n_rows + 255) / 256;
+    const int64_t blocks = row_blocks(what, logits, actions, n_rows, n_actions);
+    if (blocks <= 0) return (int)blocks;
     if (avail)
         hipLaunchKernelGGL(mdl::k_sample_avail, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, logits,
                            avail, n_rows, (int)n_actions, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)offset,
@@ -401,10 +397,7 @@ static int sample(const char* what, const float* logits, const uint8_t* avail, i
         hipLaunchKernelGGL(mdl::k_sample, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, logits, n_rows,
                            (int)n_actions, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)offset,
                            (uint32_t)(offset >> 32), offset_dev, actions, log_probs);
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return 0;
-    snprintf(msg, sizeof msg, "%s: launch failed", what);
-    return rfail(msg, e);
+    return launched(what);
 }
 
 int mdl_sample_actions(const float* logits, int64_t n_rows, int32_t n_actions, uint64_t seed, uint64_t offset,
@@ -438,24 +431,12 @@ int mdl_sample_actions_avail_dev(const float* logits, const uint8_t* avail, int6
 static int select_eps(const char* what, const float* q, const uint8_t* avail, int64_t n_rows, int32_t n_actions,
                       float epsilon, uint64_t seed, uint64_t offset, const float* epsilon_dev,
                       const uint64_t* offset_dev, uint8_t* actions, uint8_t* explored, void* stream) {
-    char msg[96];
-    if (!q || !actions) {
-        snprintf(msg, sizeof msg, "%s: null argument", what);
-        return rfail(msg);
-    }
-    if (n_rows < 0 || n_actions < 1 || n_actions > 256) {
-        snprintf(msg, sizeof msg, "%s: bad sizes", what);
-        return rfail(msg);
-    }
-    if (n_rows == 0) return 0;
-    const int64_t blocks = (n_rows + 255) / 256;
+    const int64_t blocks = row_blocks(what, q, actions, n_rows, n_actions);
+    if (blocks <= 0) return (int)blocks;
     hipLaunchKernelGGL(mdl::k_select_eps, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, q, avail, n_rows,
                        (int)n_actions, epsilon, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)offset,
                        (uint32_t)(offset >> 32), epsilon_dev, offset_dev, actions, explored);
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return 0;
-    snprintf(msg, sizeof msg, "%s: launch failed", what);
-    return rfail(msg, e);
+    return launched(what);
 }
 
 int mdl_select_actions_eps(const float* q, const uint8_t* avail, int64_t n_rows, int32_t n_actions, float epsilon,

@@ -38,6 +38,8 @@ STEP_LAYOUTS = {"auto": _lib.MDL_STEP_LAYOUT_AUTO, "wave": _lib.MDL_STEP_LAYOUT_
                 "halves": _lib.MDL_STEP_LAYOUT_HALVES}
 _LAYOUT_NAMES = {_lib.MDL_STEP_LAYOUT_WAVE: "wave", _lib.MDL_STEP_LAYOUT_ROWS: "rows", _lib.MDL_STEP_LAYOUT_HALVES: "halves"}
 STATUS_NAMES = ("None", "waiting", "in_transit", "delivered")
+OBS_KEYS = ("actor_map", "actor_vec", "critic_map", "critic_vec")
+ALT_KEYS = ("idq_obs", "qmix_state")
 
 
 def _as_grid(m):
@@ -230,12 +232,7 @@ class BatchedEnv:
         for s in shape:
             want *= s
         for t, dt, name in zip(out, (torch.float64, torch.float32, torch.uint8), ("r_env", "r_shaped", "done")):
-            if not isinstance(t, torch.Tensor) or t.dtype != dt:
-                raise TypeError(f"out {name} must be a {dt} tensor")
-            if not t.is_cuda or t.get_device() != self.device.index or not t.is_contiguous():
-                raise ValueError(f"out {name} must be contiguous on {self.device}")
-            if t.numel() < want:
-                raise ValueError(f"out {name} holds {t.numel()} entries, needs {want}")
+            self._check_vec(t, dt, f"out {name}", want)
         self._out_ok = (out[0], out[1], out[2], shape, (out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr()))
 
     def _out_ptrs(self, out, shape):
@@ -306,31 +303,38 @@ class BatchedEnv:
         if self._shape_run_end[0] < n:
             raise ValueError("step_obs: the envs mix map shapes; use step() and build_obs() per same-shape group")
         H, W = self.grids[int(self.env_map[0])].shape
-        if obs_out is None:
-            obs_out = self._obs_cache if getattr(self, "_obs_cache", None) is not None else self.obs_buffers(n, H, W)
-            self._obs_cache = obs_out
-        shapes = dict(actor_map=(n, self.A, 6, H, W), actor_vec=(n, self.A, self.actor_vec_dim),
-                      critic_map=(n, 4, H, W), critic_vec=(n, self.critic_vec_dim))
-        op = {}
-        for k in ("actor_map", "actor_vec", "critic_map", "critic_vec"):
-            t = obs_out.get(k) if k in which else None
-            if t is not None:
-                self._check_obs_out(t, k, shapes[k])
-            op[k] = None if t is None else t.data_ptr()
+        obs_out, op = self._obs_out(obs_out, which, n, H, W)
         check(lib().mdl_step_obs(self._h, actions.data_ptr(), ACTION_FORMATS[action_format], 1 if auto_reset else 0,
-                                 ptrs[0], ptrs[1], ptrs[2], op["actor_map"], op["actor_vec"], op["critic_map"],
-                                 op["critic_vec"], _raw_stream(self._dev)), "mdl_step_obs")
+                                 ptrs[0], ptrs[1], ptrs[2], *op, _raw_stream(self._dev)), "mdl_step_obs")
         self._keep = (None, actions)
         # only the outputs written by this call (a cached dict's other entries would be stale)
         return out[0], out[1], out[2], {k: (v if k in which else None) for k, v in obs_out.items()}
 
-    def _check_mask(self, t, name):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
-            raise TypeError(f"{name} must be a uint8 tensor")
+    def _check_buf(self, t, dtype, need, bad, misplaced=None, short=None):
+        """A caller's buffer: a contiguous ``dtype`` tensor on the engine's device with at least
+        ``need`` entries (an int) or of exactly the shape ``need`` (a tuple).  What is raised is the
+        call site's: ``bad`` = (exception class, message) for a wrong type or dtype and, unless the
+        site words them apart, ``misplaced`` for a wrong device or layout and ``short`` for the size
+        (its message may hold ``{n}``, the tensor's entry count)."""
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+            raise bad[0](bad[1])
         if not t.is_cuda or t.get_device() != self.device.index or not t.is_contiguous():
-            raise ValueError(f"{name} must be contiguous on {self.device}")
-        if t.numel() < self.E:
-            raise ValueError(f"{name} holds {t.numel()} entries, needs {self.E}")
+            err = misplaced or bad
+            raise err[0](err[1])
+        if (tuple(t.shape) != need) if isinstance(need, tuple) else (t.numel() < need):
+            err = short or bad
+            raise err[0](err[1].format(n=t.numel()))
+
+    def _check_vec(self, t, dtype, name, n=None):
+        """``_check_buf`` for a vector of ``n`` (default E) entries -- masks, per-env results -- in
+        the three wordings those share."""
+        n = self.E if n is None else n
+        self._check_buf(t, dtype, n, (TypeError, f"{name} must be a {dtype} tensor"),
+                        (ValueError, f"{name} must be contiguous on {self.device}"),
+                        (ValueError, f"{name} holds {{n}} entries, needs {n}"))
+
+    def _check_mask(self, t, name):
+        self._check_vec(t, torch.uint8, name)
 
     def step_episode(self, actions: torch.Tensor, active: torch.Tensor, action_format: str = "int", out=None,
                      filled: torch.Tensor | None = None, obs_out: dict | None = None,
@@ -354,23 +358,11 @@ class BatchedEnv:
             ptrs = (out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr())
         else:
             ptrs = self._out_ptrs(out, (n,))
-        if self._shape_run_end[0] < n:
-            raise ValueError("step_episode: the envs mix map shapes (build one engine per map shape)")
-        H, W = self.grids[int(self.env_map[0])].shape
-        if obs_out is None:
-            obs_out = self._obs_cache if getattr(self, "_obs_cache", None) is not None else self.obs_buffers(n, H, W)
-            self._obs_cache = obs_out
-        shapes = dict(actor_map=(n, self.A, 6, H, W), actor_vec=(n, self.A, self.actor_vec_dim),
-                      critic_map=(n, 4, H, W), critic_vec=(n, self.critic_vec_dim))
-        op = {}
-        for k in ("actor_map", "actor_vec", "critic_map", "critic_vec"):
-            t = obs_out.get(k) if k in which else None
-            if t is not None:
-                self._check_obs_out(t, k, shapes[k])
-            op[k] = None if t is None else t.data_ptr()
+        H, W = self.single_map_shape("step_episode")
+        obs_out, op = self._obs_out(obs_out, which, n, H, W)
         check(lib().mdl_step_episode(self._h, actions.data_ptr(), ACTION_FORMATS[action_format], active.data_ptr(),
-                                     ptrs[0], ptrs[1], ptrs[2], ptr(filled), op["actor_map"], op["actor_vec"],
-                                     op["critic_map"], op["critic_vec"], _raw_stream(self._dev)), "mdl_step_episode")
+                                     ptrs[0], ptrs[1], ptrs[2], ptr(filled), *op, _raw_stream(self._dev)),
+              "mdl_step_episode")
         self._keep = (None, actions)
         return out[0], out[1], out[2], {k: (v if k in which else None) for k, v in obs_out.items()}
 
@@ -464,6 +456,41 @@ class BatchedEnv:
         if t.numel() < want:
             raise ValueError(f"{name} holds {t.numel()} floats, needs {want} {tuple(shape)}")
 
+    def _obs_out(self, obs_out, which, n, H, W, strict=False):
+        """The observation outputs of one call over n envs of an [H, W] map -> (the dict, the four
+        addresses in ``OBS_KEYS`` order).  Without ``obs_out`` the engine's own cached buffers.  Only
+        the entries ``which`` names are written (the others: address None), each checked against its
+        shape; ``strict``: a named entry must be in the dict."""
+        if obs_out is None:
+            obs_out = self._obs_cache if getattr(self, "_obs_cache", None) is not None else self.obs_buffers(n, H, W)
+            self._obs_cache = obs_out
+        shapes = dict(actor_map=(n, self.A, 6, H, W), actor_vec=(n, self.A, self.actor_vec_dim),
+                      critic_map=(n, 4, H, W), critic_vec=(n, self.critic_vec_dim))
+        op = []
+        for k in OBS_KEYS:
+            t = (obs_out[k] if strict else obs_out.get(k)) if k in which else None
+            if t is not None:
+                self._check_obs_out(t, k, shapes[k])
+            op.append(ptr(t))
+        return obs_out, op
+
+    def _alt_out(self, out, n, H, W, state_shape, new=(), which=ALT_KEYS):
+        """The IDQ / qmix outputs of one call over n envs of an [H, W] map -> (the dict, the idq_obs and
+        qmix_state addresses, then oh, ow of the qmix state: ``state_shape`` (7, h, w) or the map's).
+        Without ``out``, new tensors for the entries ``new`` names.  The entries present among those
+        ``which`` names are checked against their shapes and written (the others: address None)."""
+        oh, ow = (H, W) if state_shape is None else (int(state_shape[1]), int(state_shape[2]))
+        shapes = dict(idq_obs=(n, self.A, 6, H, W), qmix_state=(n, 7, oh, ow))
+        if out is None:
+            out = {k: torch.empty(shapes[k], dtype=torch.float32, device=self.device) for k in ALT_KEYS if k in new}
+        op = []
+        for k in ALT_KEYS:
+            t = out.get(k) if k in which else None
+            if t is not None:
+                self._check_obs_out(t, k, shapes[k])
+            op.append(ptr(t))
+        return out, op + [oh, ow]
+
     def build_obs(self, env_begin: int = 0, n: int | None = None, out: dict | None = None,
                   which=("actor_map", "actor_vec", "critic_map", "critic_vec")):
         """convert_observation / generate_vector_features / convert_global_state
@@ -471,18 +498,10 @@ class BatchedEnv:
         on a range that mixes map shapes)."""
         n, g = self._obs_range(env_begin, n)
         H, W = g.shape
-        if out is None:
-            out = self.obs_buffers(n, H, W)
-        p = {k: (out[k] if k in which else None) for k in ("actor_map", "actor_vec", "critic_map", "critic_vec")}
-        shapes = dict(actor_map=(n, self.A, 6, H, W), actor_vec=(n, self.A, self.actor_vec_dim),
-                      critic_map=(n, 4, H, W), critic_vec=(n, self.critic_vec_dim))
-        for k, t in p.items():
-            if t is not None:
-                self._check_obs_out(t, k, shapes[k])
+        out, op = self._obs_out(self.obs_buffers(n, H, W) if out is None else out, which, n, H, W, strict=True)
         if n == 0:
             return out
-        check(lib().mdl_build_obs(self._h, env_begin, n, ptr(p["actor_map"]), ptr(p["actor_vec"]),
-                                  ptr(p["critic_map"]), ptr(p["critic_vec"]), self._stream()), "mdl_build_obs")
+        check(lib().mdl_build_obs(self._h, env_begin, n, *op, self._stream()), "mdl_build_obs")
         return out
 
     # ---- IDQ / qmix featurizers (SURVEY.md §8(f)2) ----
@@ -493,23 +512,10 @@ class BatchedEnv:
         state_shape (7, h, w) defaults to the map's (7, H, W) as the qmix trainer uses; build the
         engine with tracker="fresh" for the IDQ / qmix trainers' per-episode trackers."""
         n, g = self._obs_range(env_begin, n)
-        H, W = g.shape
-        oh, ow = (H, W) if state_shape is None else (int(state_shape[1]), int(state_shape[2]))
-        if out is None:
-            f = dict(dtype=torch.float32, device=self.device)
-            out = {}
-            if "idq_obs" in which:
-                out["idq_obs"] = torch.empty((n, self.A, 6, H, W), **f)
-            if "qmix_state" in which:
-                out["qmix_state"] = torch.empty((n, 7, oh, ow), **f)
-        if out.get("idq_obs") is not None:
-            self._check_obs_out(out["idq_obs"], "idq_obs", (n, self.A, 6, H, W))
-        if out.get("qmix_state") is not None:
-            self._check_obs_out(out["qmix_state"], "qmix_state", (n, 7, oh, ow))
+        out, op = self._alt_out(out, n, *g.shape, state_shape, new=which)
         if n == 0:
             return out
-        check(lib().mdl_build_obs_alt(self._h, env_begin, n, ptr(out.get("idq_obs")), ptr(out.get("qmix_state")),
-                                      oh, ow, self._stream()), "mdl_build_obs_alt")
+        check(lib().mdl_build_obs_alt(self._h, env_begin, n, *op, self._stream()), "mdl_build_obs_alt")
         return out
 
     def alt_pre_buffer(self) -> torch.Tensor:
@@ -532,43 +538,28 @@ class BatchedEnv:
         reward.  ops_are_ints=False reproduces the trainer, which hands reward_shaping string
         ops.  Returns (r_idq f64 [E, A] or None, obs dict)."""
         n = self.E
-        if self._shape_run_end[0] < n:
-            raise ValueError("alt_transition: the envs mix map shapes (build one engine per map shape)")
-        H, W = self.grids[int(self.env_map[0])].shape
-        oh, ow = (H, W) if state_shape is None else (int(state_shape[1]), int(state_shape[2]))
-        if not isinstance(pre, torch.Tensor) or pre.dtype != torch.uint8 or not pre.is_cuda \
-                or pre.get_device() != self.device.index or not pre.is_contiguous():
-            raise TypeError(f"pre must be a contiguous uint8 tensor on {self.device} (alt_pre_buffer())")
-        if pre.numel() < n * self.A * 16 + n * 4:
-            raise ValueError(f"pre holds {pre.numel()} bytes, needs {n * self.A * 16 + n * 4}")
+        H, W = self.single_map_shape("alt_transition")
+        nb = n * self.A * 16 + n * 4
+        self._check_buf(pre, torch.uint8, nb,
+                        (TypeError, f"pre must be a contiguous uint8 tensor on {self.device} (alt_pre_buffer())"),
+                        short=(ValueError, f"pre holds {{n}} bytes, needs {nb}"))
         if row_mask is not None:
             self._check_mask(row_mask, "row_mask")
-        f = dict(dtype=torch.float32, device=self.device)
-        if out is None:
-            out = {}
-            if "idq_obs" in which:
-                out["idq_obs"] = torch.empty((n, self.A, 6, H, W), **f)
-            if "qmix_state" in which:
-                out["qmix_state"] = torch.empty((n, 7, oh, ow), **f)
-        p = {k: (out.get(k) if k in which else None) for k in ("idq_obs", "qmix_state")}
-        if p["idq_obs"] is not None:
-            self._check_obs_out(p["idq_obs"], "idq_obs", (n, self.A, 6, H, W))
-        if p["qmix_state"] is not None:
-            self._check_obs_out(p["qmix_state"], "qmix_state", (n, 7, oh, ow))
+        out, op = self._alt_out(out, n, H, W, state_shape, new=which, which=which)
         if actions is not None:
             actions = self._step_args(actions, n)
             if r_out is None:
                 r_out = torch.empty((n, self.A), dtype=torch.float64, device=self.device)
-            elif r_out.dtype != torch.float64 or not r_out.is_cuda or r_out.get_device() != self.device.index \
-                    or not r_out.is_contiguous() or r_out.numel() < n * self.A:
-                raise TypeError(f"r_out must be a contiguous float64 tensor of {n * self.A} entries on {self.device}")
+            else:
+                self._check_buf(r_out, torch.float64, n * self.A, (
+                    TypeError, f"r_out must be a contiguous float64 tensor of {n * self.A} entries on {self.device}"))
         else:
             r_out = None
         check(lib().mdl_alt_transition(self._h, ptr(actions), ACTION_FORMATS[action_format], 1 if ops_are_ints else 0,
-                                       ptr(row_mask), pre.data_ptr(), ptr(r_out), ptr(p["idq_obs"]),
-                                       ptr(p["qmix_state"]), oh, ow, self._stream()), "mdl_alt_transition")
+                                       ptr(row_mask), pre.data_ptr(), ptr(r_out), *op, self._stream()),
+              "mdl_alt_transition")
         self._keep = (None, actions)
-        return r_out, {k: v for k, v in p.items() if v is not None}
+        return r_out, {k: out[k] for k in ALT_KEYS if k in which and out.get(k) is not None}
 
     def cycle_begin(self, done: torch.Tensor, out: dict | None = None, completed: torch.Tensor | None = None,
                     completed_return: torch.Tensor | None = None, completed_steps: torch.Tensor | None = None,
@@ -583,28 +574,20 @@ class BatchedEnv:
         caller's tensors (either may be missing); completed uint8, completed_return float64,
         completed_steps int32, each [E] or None.  Returns ``out``."""
         n = self.E
-        if self._shape_run_end[0] < n:
-            raise ValueError("cycle_begin: the envs mix map shapes (build one engine per map shape)")
-        H, W = self.grids[int(self.env_map[0])].shape
-        oh, ow = (H, W) if state_shape is None else (int(state_shape[1]), int(state_shape[2]))
+        H, W = self.single_map_shape("cycle_begin")
         self._check_mask(done, "done")
-        out = {} if out is None else out
-        if out.get("idq_obs") is not None:
-            self._check_obs_out(out["idq_obs"], "idq_obs", (n, self.A, 6, H, W))
-        if out.get("qmix_state") is not None:
-            self._check_obs_out(out["qmix_state"], "qmix_state", (n, 7, oh, ow))
+        out, op = self._alt_out(out, n, H, W, state_shape)
         if completed is not None:
             self._check_mask(completed, "completed")
             if completed.data_ptr() == done.data_ptr():
                 raise ValueError("completed must not be the done mask itself (the launch reads one and writes both)")
         for t, dt, name in ((completed_return, torch.float64, "completed_return"),
                             (completed_steps, torch.int32, "completed_steps")):
-            if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_cuda
-                                  or t.get_device() != self.device.index or not t.is_contiguous() or t.numel() < n):
-                raise TypeError(f"{name} must be a contiguous {dt} tensor of {n} entries on {self.device}")
+            if t is not None:
+                self._check_buf(t, dt, n, (TypeError, f"{name} must be a contiguous {dt} tensor of {n} entries on "
+                                                      f"{self.device}"))
         check(lib().mdl_cycle_begin(self._h, done.data_ptr(), ptr(completed), ptr(completed_return),
-                                    ptr(completed_steps), ptr(out.get("idq_obs")), ptr(out.get("qmix_state")),
-                                    oh, ow, self._stream()), "mdl_cycle_begin")
+                                    ptr(completed_steps), *op, self._stream()), "mdl_cycle_begin")
         return out
 
     # ---- greedy baseline (SURVEY.md §8(f)3): greedyagent.py batched on the device ----
@@ -621,9 +604,9 @@ class BatchedEnv:
         ids, n = self._ids(env_ids)
         if out is None:
             out = torch.empty((n, self.A), dtype=torch.uint8, device=self.device)
-        elif out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.numel() < n * self.A \
-                or out.get_device() != self.device.index:
-            raise ValueError(f"out must be a contiguous uint8 tensor on {self.device} of >= {n}x{self.A} entries")
+        else:
+            self._check_buf(out, torch.uint8, n * self.A, (
+                ValueError, f"out must be a contiguous uint8 tensor on {self.device} of >= {n}x{self.A} entries"))
         if n == 0:
             return out
         check(lib().mdl_greedy_actions(self._h, ptr(ids), n, ptr(out), self._stream()), "mdl_greedy_actions")
@@ -639,9 +622,9 @@ class BatchedEnv:
             self._check_mask(active, "active")
         if out is None:
             out = torch.empty((self.E, self.A), dtype=torch.uint8, device=self.device)
-        elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or not out.is_cuda \
-                or not out.is_contiguous() or out.numel() < self.E * self.A or out.get_device() != self.device.index:
-            raise ValueError(f"out must be a contiguous uint8 tensor on {self.device} of >= {self.E}x{self.A} entries")
+        else:
+            self._check_buf(out, torch.uint8, self.E * self.A, (
+                ValueError, f"out must be a contiguous uint8 tensor on {self.device} of >= {self.E}x{self.A} entries"))
         check(lib().mdl_greedy_actions_masked(self._h, ptr(active), ptr(out), self._stream()),
               "mdl_greedy_actions_masked")
         return out
@@ -660,14 +643,8 @@ class BatchedEnv:
             if len(out) != 3:
                 raise ValueError("out must be (total_reward, delivered, steps)")
             for t, dt, name in zip(out, (torch.float64, torch.int32, torch.int32), ("total_reward", "delivered", "steps")):
-                if t is None:      # an output the caller does not want
-                    continue
-                if not isinstance(t, torch.Tensor) or t.dtype != dt:
-                    raise TypeError(f"out {name} must be a {dt} tensor")
-                if not t.is_cuda or t.get_device() != self.device.index or not t.is_contiguous():
-                    raise ValueError(f"out {name} must be contiguous on {self.device}")
-                if t.numel() < self.E:
-                    raise ValueError(f"out {name} holds {t.numel()} entries, needs {self.E}")
+                if t is not None:      # None: an output the caller does not want
+                    self._check_vec(t, dt, f"out {name}")
         check(lib().mdl_episode_results(self._h, ptr(out[0]), ptr(out[1]), ptr(out[2]), self._stream()),
               "mdl_episode_results")
         return out[0], out[1], out[2]
@@ -688,9 +665,9 @@ class BatchedEnv:
         shape = (self.E, self.A, ACTION_DIM)
         if out is None:
             out = torch.empty(shape, dtype=torch.uint8, device=self.device)
-        elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or not out.is_cuda \
-                or not out.is_contiguous() or tuple(out.shape) != shape or out.get_device() != self.device.index:
-            raise ValueError(f"out must be a contiguous uint8 tensor {list(shape)} on {self.device}")
+        else:
+            self._check_buf(out, torch.uint8, shape, (
+                ValueError, f"out must be a contiguous uint8 tensor {list(shape)} on {self.device}"))
         check(lib().mdl_avail_actions(self._h, ptr(active), ptr(out), self._stream()), "mdl_avail_actions")
         return out
 

@@ -188,3 +188,76 @@ def test_step_kernel_name_table(mapname, A, P, tracker, layout, with_obs, want):
     env = _mg().BatchedEnv(grid(mapname), 8, A, P, 20, seed=1, tracker=tracker, max_packages_obs=5)
     assert env.step_kernel_name(layout, with_obs=with_obs) == want
     env.close()
+
+
+# What the parent of the shared buffer check raised, by the way a caller's buffer is wrong: a wrong
+# dtype, a non-contiguous view, one entry too few, a CPU tensor.  Read off each call site as it stood
+# before the checks were unified (every one of them is refused in Python, before any launch).
+_T, _V = TypeError, ValueError
+MASK_ERRS = dict(dtype=_T, noncontig=_V, short=_V, cpu=_V)      # uint8 [E] masks; episode_results' outputs
+OBS_ERRS = dict(dtype=_T, noncontig=_T, short=_V, cpu=_T)       # observation outputs; alt_transition's pre
+ALL_TYPE = dict(dtype=_T, noncontig=_T, short=_T, cpu=_T)       # r_out, completed_return, completed_steps
+ALL_VALUE = dict(dtype=_V, noncontig=_V, short=_V, cpu=_V)      # greedy_actions*' and avail_actions' out
+
+
+def _bad_buffers(good):
+    """The four wrong forms of a valid caller buffer."""
+    return dict(dtype=good.to(torch.int16), noncontig=torch.stack([good, good], dim=-1)[..., 0],
+                short=good.reshape(-1)[:-1], cpu=good.cpu())
+
+
+def test_caller_buffers_refused_as_before():
+    """Every public BatchedEnv method that takes a caller buffer, offered each buffer in the four
+    wrong forms: refused with the exception type its call site has always raised."""
+    E, A, P = 3, 2, 3
+    env = _mg().BatchedEnv(grid("map1.txt"), E, A, P, 20, seed=1)
+    H, W = env.single_map_shape("test")
+    z = lambda *s, dt=torch.uint8: torch.zeros(s, dtype=dt, device="cuda")   # noqa: E731
+    acts = z(E, A)
+    obs = env.obs_buffers()
+    alt = dict(idq_obs=z(E, A, 6, H, W, dt=torch.float32), qmix_state=z(E, 7, H, W, dt=torch.float32))
+    res = (z(E, dt=torch.float64), z(E, dt=torch.int32), z(E, dt=torch.int32))
+    pre, done = env.alt_pre_buffer(), z(E)
+
+    def with_res(i, t):
+        return tuple(t if k == i else r for k, r in enumerate(res))
+
+    # (what is offered, the valid buffer, the call with a replacement for it, the parent's exceptions)
+    table = []
+    for k in obs:
+        table += [(f"step_obs obs_out[{k}]", obs[k], lambda t, k=k: env.step_obs(acts, obs_out={**obs, k: t}), OBS_ERRS),
+                  (f"step_episode obs_out[{k}]", obs[k],
+                   lambda t, k=k: env.step_episode(acts, z(E), obs_out={**obs, k: t}), OBS_ERRS),
+                  (f"build_obs out[{k}]", obs[k], lambda t, k=k: env.build_obs(out={**obs, k: t}), OBS_ERRS)]
+    for k in alt:
+        table += [(f"build_obs_alt out[{k}]", alt[k], lambda t, k=k: env.build_obs_alt(out={**alt, k: t}), OBS_ERRS)]
+    table += [
+        ("step_episode active", z(E), lambda t: env.step_episode(acts, t), MASK_ERRS),
+        ("step_episode filled", z(E), lambda t: env.step_episode(acts, z(E), filled=t), MASK_ERRS),
+        ("alt_transition pre", pre, lambda t: env.alt_transition(acts, t), OBS_ERRS),
+        ("alt_transition row_mask", z(E), lambda t: env.alt_transition(acts, pre, row_mask=t), MASK_ERRS),
+        ("alt_transition r_out", z(E, A, dt=torch.float64), lambda t: env.alt_transition(acts, pre, r_out=t), ALL_TYPE),
+        ("cycle_begin done", done, lambda t: env.cycle_begin(t), MASK_ERRS),
+        ("cycle_begin completed", z(E), lambda t: env.cycle_begin(done, completed=t), MASK_ERRS),
+        ("cycle_begin completed_return", res[0], lambda t: env.cycle_begin(done, completed_return=t), ALL_TYPE),
+        ("cycle_begin completed_steps", res[1], lambda t: env.cycle_begin(done, completed_steps=t), ALL_TYPE),
+        ("greedy_actions out", z(E, A), lambda t: env.greedy_actions(out=t), ALL_VALUE),
+        ("greedy_actions_masked active", z(E), lambda t: env.greedy_actions_masked(t), MASK_ERRS),
+        ("greedy_actions_masked out", z(E, A), lambda t: env.greedy_actions_masked(z(E), out=t), ALL_VALUE),
+        ("avail_actions active", z(E), lambda t: env.avail_actions(t), MASK_ERRS),
+        ("avail_actions out", z(E, A, 15), lambda t: env.avail_actions(out=t), ALL_VALUE),
+    ]
+    for i, name in enumerate(("total_reward", "delivered", "steps")):
+        table += [(f"episode_results out {name}", res[i], lambda t, i=i: env.episode_results(with_res(i, t)), MASK_ERRS)]
+    wrong = []
+    for what, good, call, errs in table:
+        for case, t in _bad_buffers(good).items():
+            try:
+                call(t)
+                got = None
+            except Exception as e:   # noqa: BLE001 -- the type is what is under test
+                got = type(e)
+            if got is not errs[case]:
+                wrong.append(f"{what}, {case}: {getattr(got, '__name__', got)}, not {errs[case].__name__}")
+    assert not wrong, "\n".join(wrong)
+    env.close()
