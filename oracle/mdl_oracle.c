@@ -36,6 +36,11 @@
 typedef struct {
     uint32_t key[MT_N];
     int pos;
+    /* read-only counters of the draw stream (or_env_counters): tests assert on them that their
+     * inputs reach the stream's edges; nothing here reads them */
+    uint64_t words;     /* 32-bit words produced (a refill falls where words / 624 changes) */
+    uint64_t rejected;  /* words the masked rejection threw away */
+    uint64_t retries;   /* target == start redraws (env.py:107-111) */
 } OMT;
 
 static void mt_seed(OMT* mt, uint32_t seed) {
@@ -66,6 +71,7 @@ static void mt_gen(OMT* mt) {
 static uint32_t mt_next32(OMT* mt) {
     if (mt->pos == MT_N) mt_gen(mt);
     uint32_t y = mt->key[mt->pos++];
+    mt->words++;
     y ^= (y >> 11);
     y ^= (y << 7) & 0x9d2c5680UL;
     y ^= (y << 15) & 0xefc60000UL;
@@ -83,8 +89,7 @@ static long or_randint(OMT* mt, long lo, long hi) {
     uint32_t mask = (uint32_t)rng;
     mask |= mask >> 1; mask |= mask >> 2; mask |= mask >> 4; mask |= mask >> 8; mask |= mask >> 16;
     uint32_t v;
-    while ((v = (mt_next32(mt) & mask)) > (uint32_t)rng) {
-    }
+    while ((v = (mt_next32(mt) & mask)) > (uint32_t)rng) mt->rejected++;
     return lo + (long)v;
 }
 
@@ -157,6 +162,7 @@ void or_env_reset(OEnv* e) {
         for (;;) {
             target = e->free_cells[or_randint(&e->mt, 0, nfp)];
             if (start != target) break;
+            e->mt.retries++;
         }
         long to_deadline = 10 + or_randint(&e->mt, (long)(N / 2), 3L * N); /* int(N/2) */
         int start_time = (i <= lim) ? 0 : (int)or_randint(&e->mt, 1, e->T);
@@ -197,6 +203,11 @@ OEnv* or_env_new(const uint8_t* grid, int H, int W, int A, int P, int T,
     mt_seed(&e->mt, seed);      /* env.py:40 */
     or_env_reset(e);            /* env.py:41: the constructor draws one layout */
     return e;
+}
+
+/* the generator's counters since construction: words, rejected, retries */
+void or_env_counters(const OEnv* e, uint64_t* out) {
+    out[0] = e->mt.words; out[1] = e->mt.rejected; out[2] = e->mt.retries;
 }
 
 void or_env_free(OEnv* e) {

@@ -47,6 +47,7 @@ def lib():
         L.or_env_step.restype = i32
         L.or_env_step.argtypes = [vp, vp, vp, P(f64), P(i32)]
         L.or_env_get.argtypes = [vp, P(i32), P(f64), vp, vp]
+        L.or_env_counters.argtypes = [vp, vp]
         L.or_trk_new.restype = vp
         L.or_trk_new.argtypes = [i32]
         L.or_trk_free.argtypes = [vp]
@@ -129,6 +130,14 @@ class OracleEnv:
         pk = np.zeros((self.P, 8), np.int32)
         lib().or_env_get(self.h, C.byref(t), C.byref(tot), _p(rob), _p(pk))
         return dict(t=t.value, total_reward=tot.value, robots=rob, pkgs=pk)
+
+    def counters(self):
+        """The generator's read-only counters since construction: dict of words (32-bit words
+        produced; a refill falls where words // 624 changes), rejected (words the masked rejection
+        threw away) and retries (target == start redraws)."""
+        out = np.zeros(3, np.uint64)
+        lib().or_env_counters(self.h, _p(out))
+        return dict(words=int(out[0]), rejected=int(out[1]), retries=int(out[2]))
 
     def robots1(self):
         s = self.state()

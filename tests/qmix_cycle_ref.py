@@ -29,6 +29,14 @@ CASES = {
                            counts=(10, 26, 17, 2, 28)),
     "map2-delivering": dict(cfg=("map2.txt", 3, 70, 14, 7), seed=1, steps=40, marks={4: [2, 3]},
                             counts=(5, 35, 14, 1, 26)),
+    # one run per wider package chunking of the lazy reset (P = 129, 257, 513: four, eight, sixteen chunks of
+    # 64), which tests/launch_matrix.py covers call by call; counts from the oracle alone, as above
+    "map1-nch4": dict(cfg=("map1.txt", 5, 129, 12, 5), seed=81, steps=30, marks={3: [1, 4], 17: [0]},
+                      counts=(7, 23, 10, 1, 61)),
+    "map-nch8": dict(cfg=("map.txt", 3, 257, 10, 6), seed=81, steps=24, marks={2: [0, 5], 9: [3]},
+                     counts=(7, 17, 11, 1, 46)),
+    "map3-nch16": dict(cfg=("map3.txt", 3, 513, 12, 5), seed=11, steps=28, marks={4: [2, 3]},
+                       counts=(4, 24, 8, 0, 37)),
 }
 DELIVERING = ("map1-delivering", "map-delivering", "map2-delivering")
 

@@ -527,3 +527,136 @@ def test_product_sources_have_no_variant_switches():
                 seen.add(name)
                 assert name in fenced or name == "MDL_ENGINE_H", (path, m.group(0))
     assert {"MDL_ABLATE", "MDL_STAMPS"} <= seen
+
+
+# ---- tests/launch_matrix.py: the seeding, reset, tracker-clear, cycle-begin and alt-builder kernels ----
+LAUNCH_KERNELS = ("k_seed", "k_reset", "k_tracker_clear", "k_cycle_begin", "k_alt_obs", "k_alt_transition")
+
+
+def _launch_mangled_prefix(symbol):
+    """Itanium mangling of a launch-matrix symbol: a plain function's nested name, or _mangled_prefix."""
+    if "<" in symbol:
+        return _mangled_prefix(symbol)
+    name = symbol[len("mdl::"):]
+    return f"_ZN3mdl{len(name)}{name}E"
+
+
+@pytest.mark.skipif(not os.path.exists(f"{LLVM_BIN}/llvm-readelf"), reason="ROCm LLVM tools absent")
+def test_launch_matrix_lists_every_launch_kernel(tmp_path):
+    """The kernels of the six names above in the library's gfx950 code objects are exactly the 21 symbols of
+    tests/launch_matrix.py (k_seed, five k_reset, k_tracker_clear, ten k_cycle_begin, two k_alt_obs, two
+    k_alt_transition), each of which test_gpu_launch_matrix.py runs against the oracle.  A kernel added
+    to a dispatch without a matrix entry, or an entry the library no longer holds, fails here."""
+    from collections import Counter
+
+    import launch_matrix
+    from marl_gpu import _lib
+    res = _kernel_resources(_lib.LIB_PATH, tmp_path)
+    pat = re.compile(r"^_ZN3mdl\d+(?:%s)[IE]" % "|".join(LAUNCH_KERNELS))
+    built = sorted(n for n in res if pat.match(n))
+    cxxfilt = f"{LLVM_BIN}/llvm-cxxfilt"
+    if os.path.exists(cxxfilt):
+        out = subprocess.run([cxxfilt] + built, capture_output=True, text=True, check=True).stdout.split("\n")
+        have = [re.sub(r"^void ", "", d.split("(")[0]) for d in out if d]
+    else:   # no demangler: match each symbol's mangled name + template arguments
+        by_prefix = {_launch_mangled_prefix(s): s for s in launch_matrix.SYMBOLS}
+        have = [next((s for p, s in by_prefix.items() if n.startswith(p)), n) for n in built]
+    assert len(have) == len(set(have)) == len(built), Counter(have).most_common(3)
+    want = set(launch_matrix.SYMBOLS)
+    excluded = launch_matrix.EXCLUDED
+    assert not (excluded & want), "an excluded symbol has a matrix entry again: drop the exclusion"
+    assert set(have) - excluded == want, (sorted(set(have) - excluded - want), sorted(want - set(have)))
+    if not excluded:
+        kinds = Counter(s.split("<")[0] for s in want)
+        assert len(want) == 21 and kinds == {"mdl::k_seed": 1, "mdl::k_reset": 5, "mdl::k_tracker_clear": 1,
+                                             "mdl::k_cycle_begin": 10, "mdl::k_alt_obs": 2, "mdl::k_alt_transition": 2}
+    for s in launch_matrix.SYMBOLS:   # the mangling rule the fallback uses holds for every symbol
+        assert any(n.startswith(_launch_mangled_prefix(s)) for n in built), s
+
+
+def test_launch_matrix_shapes_select_their_symbols():
+    """Each launch-matrix entry's shape selects its symbol by the dispatch rules (restated here: nch_for,
+    launch_reset, launch_cycle_begin, launch_alt_obs, launch_alt_transition), fits its map and keeps to
+    the small shapes; the table runs both edges of every package-chunk class through k_reset with each
+    class in both tracker modes, and through k_cycle_begin across the two modes, and spreads A and maps."""
+    import launch_matrix as LM
+    from golden_io import grid
+    edges = {1: (1, 64), 2: (65, 128), 4: (129, 256), 8: (257, 512), 16: (513, 1024)}
+    reset_seen, cycle_seen, mail_modes = set(), {}, set()
+    for c in LM.CASES:
+        st = {"mappo": "true", "fresh": "false"}[c.tracker]
+        nch = next(k for k, (_, hi) in edges.items() if c.P <= hi)
+        assert c.P in edges[nch], c
+        free = int((grid(c.map) == 0).sum())
+        assert free >= max(c.A, 2) and (3 if c.kind == "alt" else 4) <= c.E <= 8 and c.T == 25, c
+        assert c.map == LM.S64 or c.A < 64, c
+        if c.kind == "seed":
+            want = "mdl::k_seed"
+        elif c.kind == "reset" and c.symbol == "mdl::k_tracker_clear":
+            assert c.tracker == "mappo", c       # the stale cases are the ones that clear mid-episode
+            want = c.symbol
+        elif c.kind == "reset":
+            want = f"mdl::k_reset<{nch}>"
+            assert sum(c.rounds[:2]) == c.T - 1 and sum(c.rounds) - c.rounds[0] < c.T, c   # see launch_ref.reset_ids
+            if c.mail:
+                mail_modes.add(c.tracker)
+            else:
+                reset_seen.add((nch, c.P, c.tracker))
+        elif c.kind == "cycle":
+            want = f"mdl::k_cycle_begin<{st}, {nch}>"
+            assert cycle_seen.setdefault(c.symbol, c.P) == c.P, c   # one case per symbol
+        else:
+            assert c.kind == "alt" and c.symbol.split("<")[0] in ("mdl::k_alt_obs", "mdl::k_alt_transition"), c
+            want = f"{c.symbol.split('<')[0]}<{st}>"
+        assert c.symbol == want, (c, want)
+    for nch, (lo, hi) in edges.items():
+        modes = {p: {t for n, q, t in reset_seen if q == p} for p in (lo, hi)}
+        assert all(modes.values()) and modes[lo] | modes[hi] == {"mappo", "fresh"}, (nch, modes)
+        cyc = {p for s, p in cycle_seen.items() if s.endswith(f", {nch}>")}
+        assert cyc == {lo, hi}, (nch, cyc)
+    assert mail_modes == {"mappo", "fresh"}
+    assert len(cycle_seen) == 10
+    assert {c.A for c in LM.CASES} >= {1, 5, 8, 9, 16, 17, 64}
+    assert {c.map for c in LM.CASES} == {LM.M0, LM.M1, LM.M3, LM.S64}
+    assert any(c.kind == "cycle" and c.map == LM.S64 and c.P == 1024 for c in LM.CASES)
+    alt = [c for c in LM.CASES if c.kind == "alt" and c.tracker == "mappo"]
+    hw = {c.map: grid(c.map).size for c in alt}
+    assert LM.M0 in hw and hw[LM.M0] % 4 and any(v % 4 == 0 for v in hw.values())   # general and fast emit
+    assert any((c.A, c.P) == (16, 129) for c in alt) and any(c.map == LM.S64 for c in alt)
+
+
+def _launch_case_params():
+    import launch_matrix as LM
+    return dict(argvalues=LM.CASES, ids=[LM.case_id(c) for c in LM.CASES])
+
+
+@pytest.mark.parametrize("case", **_launch_case_params())
+def test_launch_matrix_inputs_reach_their_kernels(case):
+    """The input conditions of every launch-matrix case, from the oracle's trace alone (the GPU test
+    asserts the same before it runs the engine): stale reset cases reset trackers that hold in-transit
+    rows, survivors of earlier episodes and ids in the upper chunks; alt cases featurise survivors."""
+    import launch_ref as R
+    import oracle as O
+    O.build()
+    if case.kind in ("seed", "reset"):
+        R.check_reset_inputs(case, R.reset_trace(case))
+    elif case.kind == "cycle":
+        R.check_cycle_inputs(case, R.cycle_trace(case))
+    else:
+        R.check_alt_inputs(case, R.alt_trace(case))
+
+
+def _storm_names():
+    import launch_ref as R
+    return sorted(R.STORM)
+
+
+@pytest.mark.parametrize("name", _storm_names())
+def test_reset_storm_reaches_the_draw_stream_edges(name):
+    """The oracle generator's counters over each storm of explicit resets: refills inside and across
+    resets, masked rejections, target == start retries and the randint ranges of one value that draw
+    nothing -- what test_gpu_launch_matrix.py::test_reset_storm then runs the engine against."""
+    import launch_ref as R
+    import oracle as O
+    O.build()
+    R.check_storm_inputs(name, R.storm_trace(name))
