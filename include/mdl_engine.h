@@ -492,6 +492,28 @@ int mdl_gae(const float* rewards, const float* values, const float* next_value, 
 int mdl_build_obs(MdlEngine* eng, int32_t env_begin, int32_t n, float* actor_map, float* actor_vec,
                   float* critic_map, float* critic_vec, void* stream);
 
+/* The element type of the four observation tensors of mdl_build_obs_as / mdl_step_obs_as.  F16 (IEEE
+ * binary16) and BF16: every element is the float32 value mdl_build_obs writes, rounded once to
+ * nearest-even (ties to even, signed zeros and fp16 subnormals kept) -- bit for bit the float32
+ * tensor converted on the host. */
+#define MDL_OBS_F32 0
+#define MDL_OBS_F16 1
+#define MDL_OBS_BF16 2
+
+/* mdl_build_obs with the outputs' element type `dtype` (MDL_OBS_*; the tensors' shapes are
+ * mdl_build_obs's, their elements 2 bytes for the half types, 2-byte aligned at least).  MDL_OBS_F32
+ * is mdl_build_obs itself; an unknown dtype fails with a message. */
+int mdl_build_obs_as(MdlEngine* eng, int32_t env_begin, int32_t n, int32_t dtype, void* actor_map, void* actor_vec,
+                     void* critic_map, void* critic_vec, void* stream);
+
+/* mdl_step_obs with the observations' element type `dtype`.  MDL_OBS_F32 is mdl_step_obs itself (its
+ * one-launch form where that applies); the half types always run mdl_step's launch followed by the
+ * builder's (there is no fused half kernel).  Rewards, done and the engine's state do not depend on
+ * dtype. */
+int mdl_step_obs_as(MdlEngine* eng, const uint8_t* actions, int32_t action_format, int32_t auto_reset, double* r_env,
+                    float* r_shaped, uint8_t* done, int32_t dtype, void* actor_map, void* actor_vec,
+                    void* critic_map, void* critic_vec, void* stream);
+
 /* State snapshot into caller DEVICE buffers (async on `stream`).  Any pointer may be NULL.
  *   robots   int32 [E][A][3]  (row, col, carrying), 0-indexed
  *   pkgs     int32 [E][P][8]  (sr, sc, tr, tc, start_time, deadline, id, status 0 None/1 waiting/2 in_transit/3 delivered)

@@ -209,11 +209,12 @@ struct MdlEngine {
     // Every observation build goes through here: the env range must lie inside one run of
     // same-shape envs (the small builder copies the rank table of the range's first env's map
     // into LDS for the whole launch, mdl_obs_small.hpp k_obs_small; the outputs have one H x W).
-    hipError_t launch_obs(int env_begin, int n, float* am, float* av, float* cm, float* cv, hipStream_t s,
-                          const uint8_t* mask = nullptr) const {
+    // dtype: the outputs' element type (MDL_OBS_*), checked by the caller.
+    hipError_t launch_obs(int env_begin, int n, void* am, void* av, void* cm, void* cv, hipStream_t s,
+                          const uint8_t* mask = nullptr, int dtype = MDL_OBS_F32) const {
         if (env_begin < 0 || n <= 0 || env_begin + n > p.E || shape_run_end[env_begin] < env_begin + n)
             return hipErrorInvalidValue;
-        return mdl::launch_obs(p, env_begin, n, am, av, cm, cv, wpb_obs, lds_obs, s, obs_rank_lds, mask);
+        return mdl::launch_obs(p, env_begin, n, am, av, cm, cv, wpb_obs, lds_obs, s, obs_rank_lds, mask, dtype);
     }
     // The per-wave LDS slice of the one-launch step + observation kernels (mdl_step_obs,
     // mdl_step_episode): the reset scratch, then the planes.  0 where they do not apply (the general
@@ -612,30 +613,56 @@ int mdl_step_floor(MdlEngine* eng, int32_t n, void* stream) {
     return 0;
 }
 
-int mdl_step_obs(MdlEngine* eng, const uint8_t* actions, int32_t action_format, int32_t auto_reset, double* r_env,
-                 float* r_shaped, uint8_t* done, float* actor_map, float* actor_vec, float* critic_map,
-                 float* critic_vec, void* stream) {
-    if (!eng || !actions) return fail("mdl_step_obs: null argument");
-    if (!eng->seeded) return fail("mdl_step_obs: engine not seeded (call mdl_seed first)");
+static_assert(MDL_OBS_F32 == mdl::OBS_F32 && MDL_OBS_F16 == mdl::OBS_F16 && MDL_OBS_BF16 == mdl::OBS_BF16,
+              "mdl_kernels.hpp restates MDL_OBS_*");
+
+static bool obs_dtype_ok(int32_t dtype) {
+    return dtype == MDL_OBS_F32 || dtype == MDL_OBS_F16 || dtype == MDL_OBS_BF16;
+}
+
+// mdl_step_obs / mdl_step_obs_as (`who` names the entry in messages).  Half outputs have no fused
+// kernel: the step launch, then the builder's.
+static int step_obs_as(const char* who, MdlEngine* eng, const uint8_t* actions, int32_t action_format,
+                       int32_t auto_reset, double* r_env, float* r_shaped, uint8_t* done, int32_t dtype,
+                       void* actor_map, void* actor_vec, void* critic_map, void* critic_vec, void* stream) {
+    if (!eng || !actions) return fail("%s: null argument", who);
+    if (!eng->seeded) return fail("%s: engine not seeded (call mdl_seed first)", who);
     if (action_format != MDL_ACTION_TRAINER_INT && action_format != MDL_ACTION_CODES)
-        return fail("mdl_step_obs: unknown action_format %d", action_format);
+        return fail("%s: unknown action_format %d", who, action_format);
+    if (!obs_dtype_ok(dtype)) return fail("%s: unknown observation dtype %d (MDL_OBS_F32 / F16 / BF16)", who, dtype);
     const int E = eng->p.E;
     if (eng->shape_run_end[0] < E)
-        return fail("mdl_step_obs: the envs mix map shapes (same-shape run ends at %d); use mdl_step + mdl_build_obs "
-                    "per group", eng->shape_run_end[0]);
+        return fail("%s: the envs mix map shapes (same-shape run ends at %d); use mdl_step + mdl_build_obs "
+                    "per group", who, eng->shape_run_end[0]);
     DeviceGuard dg(eng->device);
     hipStream_t s = (hipStream_t)stream;
-    if (const size_t lds = eng->fused_obs_lds()) {   // else: the two-launch path below
+    const size_t lds = dtype == MDL_OBS_F32 ? eng->fused_obs_lds() : 0;
+    if (lds) {   // else: the two-launch path below
         const int wpb = step_wpb(E, eng->n_cu, lds, eng->p.P);
         HIPCHK(mdl::launch_step_obs(eng->p, actions, action_format, E, auto_reset, r_env, r_shaped, done,
-                                    actor_map, actor_vec, critic_map, critic_vec, wpb, lds, s));
+                                    (float*)actor_map, (float*)actor_vec, (float*)critic_map, (float*)critic_vec, wpb,
+                                    lds, s));
         return 0;
     }
     const auto sh = eng->step_shape(MDL_STEP_LAYOUT_WAVE, E);
     HIPCHK(mdl::launch_step(eng->p, actions, action_format, nullptr, E, auto_reset, r_env, r_shaped, done, sh.wpb,
                             sh.lds, s));
-    HIPCHK(eng->launch_obs(0, E, actor_map, actor_vec, critic_map, critic_vec, s));
+    HIPCHK(eng->launch_obs(0, E, actor_map, actor_vec, critic_map, critic_vec, s, nullptr, dtype));
     return 0;
+}
+
+int mdl_step_obs(MdlEngine* eng, const uint8_t* actions, int32_t action_format, int32_t auto_reset, double* r_env,
+                 float* r_shaped, uint8_t* done, float* actor_map, float* actor_vec, float* critic_map,
+                 float* critic_vec, void* stream) {
+    return step_obs_as("mdl_step_obs", eng, actions, action_format, auto_reset, r_env, r_shaped, done, MDL_OBS_F32,
+                       actor_map, actor_vec, critic_map, critic_vec, stream);
+}
+
+int mdl_step_obs_as(MdlEngine* eng, const uint8_t* actions, int32_t action_format, int32_t auto_reset, double* r_env,
+                    float* r_shaped, uint8_t* done, int32_t dtype, void* actor_map, void* actor_vec,
+                    void* critic_map, void* critic_vec, void* stream) {
+    return step_obs_as("mdl_step_obs_as", eng, actions, action_format, auto_reset, r_env, r_shaped, done, dtype,
+                       actor_map, actor_vec, critic_map, critic_vec, stream);
 }
 
 int mdl_step_episode(MdlEngine* eng, const uint8_t* actions, int32_t action_format, uint8_t* active, double* r_env,
@@ -1053,17 +1080,31 @@ int mdl_load_state(MdlEngine* eng, const void* buf, int64_t bytes, void* stream)
     return 0;
 }
 
-int mdl_build_obs(MdlEngine* eng, int32_t env_begin, int32_t n, float* actor_map, float* actor_vec,
-                  float* critic_map, float* critic_vec, void* stream) {
-    if (!eng) return fail("mdl_build_obs: null engine");
-    if (env_begin < 0 || n < 0 || env_begin + n > eng->p.E) return fail("mdl_build_obs: env range out of bounds");
+static int build_obs_as(const char* who, MdlEngine* eng, int32_t env_begin, int32_t n, int32_t dtype, void* actor_map,
+                        void* actor_vec, void* critic_map, void* critic_vec, void* stream) {
+    if (!eng) return fail("%s: null engine", who);
+    if (!obs_dtype_ok(dtype)) return fail("%s: unknown observation dtype %d (MDL_OBS_F32 / F16 / BF16)", who, dtype);
+    if (env_begin < 0 || n < 0 || env_begin + n > eng->p.E) return fail("%s: env range out of bounds", who);
     if (n == 0) return 0;
     if (eng->shape_run_end[env_begin] < env_begin + n)
-        return fail("mdl_build_obs: envs [%d, %d) mix map shapes (same-shape run ends at %d)", env_begin,
-                    env_begin + n, eng->shape_run_end[env_begin]);
+        return fail("%s: envs [%d, %d) mix map shapes (same-shape run ends at %d)", who, env_begin, env_begin + n,
+                    eng->shape_run_end[env_begin]);
     DeviceGuard dg(eng->device);
-    HIPCHK(eng->launch_obs(env_begin, n, actor_map, actor_vec, critic_map, critic_vec, (hipStream_t)stream));
+    HIPCHK(eng->launch_obs(env_begin, n, actor_map, actor_vec, critic_map, critic_vec, (hipStream_t)stream, nullptr,
+                           dtype));
     return 0;
+}
+
+int mdl_build_obs(MdlEngine* eng, int32_t env_begin, int32_t n, float* actor_map, float* actor_vec,
+                  float* critic_map, float* critic_vec, void* stream) {
+    return build_obs_as("mdl_build_obs", eng, env_begin, n, MDL_OBS_F32, actor_map, actor_vec, critic_map, critic_vec,
+                        stream);
+}
+
+int mdl_build_obs_as(MdlEngine* eng, int32_t env_begin, int32_t n, int32_t dtype, void* actor_map, void* actor_vec,
+                     void* critic_map, void* critic_vec, void* stream) {
+    return build_obs_as("mdl_build_obs_as", eng, env_begin, n, dtype, actor_map, actor_vec, critic_map, critic_vec,
+                        stream);
 }
 
 int mdl_read_state(MdlEngine* eng, int32_t* robots, int32_t* pkgs, int32_t* t, double* total_reward,

@@ -105,6 +105,119 @@ __device__ inline void emit(float* dst, int n, const F& value) {
     if (tail + lane < n) dst[tail + lane] = value(tail + lane);
 }
 
+// ---- half-precision outputs ----
+// The builders write float32, or IEEE fp16 / bfloat16 elements (f16_t / bf16_t: the element's 16
+// bits): each the float32 value rounded once to nearest-even, the conversion the hardware's
+// v_cvt_f16_f32 / v_cvt_pk_bf16_f32 make (fp16 subnormals kept: the kernels' 16-bit denormal mode
+// is the compiler's default, no flush).  Map values are 0 or 1: 1.0 is 0x3C00 / 0x3F80.
+struct f16_t {
+    uint16_t u;
+};
+struct bf16_t {
+    uint16_t u;
+};
+template <class T>
+struct is_half_out {
+    static constexpr bool value = false;
+};
+template <>
+struct is_half_out<f16_t> {
+    static constexpr bool value = true;
+};
+template <>
+struct is_half_out<bf16_t> {
+    static constexpr bool value = true;
+};
+template <class T>
+__device__ __forceinline__ T out_cvt(float x);
+template <>
+__device__ __forceinline__ float out_cvt<float>(float x) {
+    return x;
+}
+template <>
+__device__ __forceinline__ f16_t out_cvt<f16_t>(float x) {
+    return f16_t{__builtin_bit_cast(uint16_t, (_Float16)x)};
+}
+template <>
+__device__ __forceinline__ bf16_t out_cvt<bf16_t>(float x) {
+    return bf16_t{__builtin_bit_cast(uint16_t, (__bf16)x)};
+}
+// elements a (low half) and b of one dword
+template <class T>
+__device__ __forceinline__ uint32_t out_pack2(float a, float b) {
+    return (uint32_t)out_cvt<T>(a).u | ((uint32_t)out_cvt<T>(b).u << 16);
+}
+template <class T>
+__host__ __device__ constexpr uint32_t half_one();
+template <>
+__host__ __device__ constexpr uint32_t half_one<f16_t>() {
+    return 0x3C00u;
+}
+template <>
+__host__ __device__ constexpr uint32_t half_one<bf16_t>() {
+    return 0x3F80u;
+}
+// bits 0..7 of b as eight elements (0 or 1.0), two per dword: bit pair x -> (x & 1) in the low half,
+// (x >> 1) in the high one, times the pattern of 1.0 (no carries: the pattern is below 2^16)
+template <class T>
+__device__ __forceinline__ uint4 half8_of_bits(uint32_t b) {
+    auto two = [](uint32_t x) -> uint32_t { return ((x & 1u) | ((x & 2u) << 15)) * half_one<T>(); };
+    return make_uint4(two(b), two(b >> 2), two(b >> 4), two(b >> 6));
+}
+
+// n elements value(i) (float32, rounded on the way out) to dst, any 2-byte alignment: element head
+// to 16-B alignment (up to seven), 16-B body of eight elements per lane per pass, element tail.
+template <class T, class F>
+__device__ __forceinline__ void emit_h(T* dst, int n, const F& value) {
+    const int lane = lane_id();
+    int head = (int)(((16 - ((uintptr_t)dst & 15)) & 15) >> 1);
+    if (head > n) head = n;
+    if (lane < head) dst[lane] = out_cvt<T>(value(lane));
+    const int nb = (n - head) >> 3;
+    uint4* d4 = reinterpret_cast<uint4*>(dst + head);
+    for (int q = lane; q < nb; q += WAVE) {
+        const int i0 = head + 8 * q;
+        // One dword (two values) per trip of a loop kept rolled: two inlined copies of value(), each
+        // with its own divergent branches, instead of eight -- k_obs_h must have no SGPR spill and no
+        // scratch.  k is uniform: the selects below are scalar.
+        uint32_t v0 = 0, v1 = 0, v2 = 0, v3 = 0;
+#pragma unroll 1
+        for (int k = 0; k < 4; k++) {
+            const uint32_t d = out_pack2<T>(value(i0 + 2 * k), value(i0 + 2 * k + 1));
+            v0 = k == 0 ? d : v0;
+            v1 = k == 1 ? d : v1;
+            v2 = k == 2 ? d : v2;
+            v3 = k == 3 ? d : v3;
+        }
+        d4[q] = make_uint4(v0, v1, v2, v3);
+    }
+    const int tail = head + 8 * nb;
+    if (tail + lane < n) dst[tail + lane] = out_cvt<T>(value(tail + lane));
+}
+template <class F>
+__device__ __forceinline__ void emit(f16_t* dst, int n, const F& value) {
+    emit_h(dst, n, value);
+}
+template <class F>
+__device__ __forceinline__ void emit(bf16_t* dst, int n, const F& value) {
+    emit_h(dst, n, value);
+}
+
+// The same for 0/1 elements given as bits: bits(i) holds element i in bit 0 and, where i + 8 <= n,
+// elements i..i+7 in bits 0..7.
+template <class T, class F>
+__device__ __forceinline__ void emit_bits_h(T* dst, int n, const F& bits) {
+    const int lane = lane_id();
+    int head = (int)(((16 - ((uintptr_t)dst & 15)) & 15) >> 1);
+    if (head > n) head = n;
+    if (lane < head) dst[lane] = T{(uint16_t)((bits(lane) & 1u) * half_one<T>())};
+    const int nb = (n - head) >> 3;
+    uint4* d4 = reinterpret_cast<uint4*>(dst + head);
+    for (int q = lane; q < nb; q += WAVE) d4[q] = half8_of_bits<T>(bits(head + 8 * q));
+    const int tail = head + 8 * nb;
+    if (tail + lane < n) dst[tail + lane] = T{(uint16_t)((bits(tail + lane) & 1u) * half_one<T>())};
+}
+
 // Stage robots / cell flags / carriers / critic id order.  Robots come in on
 // lanes (lane a < A): cell packed r|c<<8, carry id.
 template <class Trk>
@@ -501,10 +614,28 @@ __device__ inline void emit_maps_bitrows(const FeatLds& L, int NW, int HW, int A
 
 // convert_observation for agents [a0, a0+na): dst [na][6][H][W].
 // a_valid=false reproduces the early return (channel 0 only).
-__device__ inline void emit_actor_maps(const FeatCtx& c, const FeatLds& L, int a0, int na, bool a_valid, float* dst) {
+// (half elements: eight per lane where HW % 8 == 0 and dst is 16-B aligned, else element by element)
+template <class T>
+__device__ inline void emit_actor_maps(const FeatCtx& c, const FeatLds& L, int a0, int na, bool a_valid, T* dst) {
     const int HW = c.HW, NW = c.NW;
     const int lane = lane_id();
-    if ((HW & 3) == 0 && (((uintptr_t)dst) & 15) == 0) {
+    if constexpr (is_half_out<T>::value) {
+        if ((HW & 7) == 0 && (((uintptr_t)dst) & 15) == 0) {
+            const int qpp = HW >> 3;
+            const float inv_qpp = 1.0f / (float)qpp;
+            const int nq = na * 6 * qpp;
+            uint4* d4 = reinterpret_cast<uint4*>(dst);
+            for (int q = lane; q < nq; q += WAVE) {
+                const int plane = fdivi(q, qpp, inv_qpp);
+                const int c0 = (q - plane * qpp) << 3;
+                const int al = plane / 6;
+                const int ch = plane - 6 * al;
+                d4[q] = half8_of_bits<T>(actor_bits4(L, NW, a0 + al, ch, c0, a_valid) |
+                                         (actor_bits4(L, NW, a0 + al, ch, c0 + 4, a_valid) << 4));
+            }
+            return;
+        }
+    } else if ((HW & 3) == 0 && (((uintptr_t)dst) & 15) == 0) {
         // float4 per lane, never straddling a plane: 1 KiB per wave store
         const int qpp = HW >> 2;
         const float inv_qpp = 1.0f / (float)qpp;
@@ -541,10 +672,24 @@ __device__ inline void emit_actor_maps(const FeatCtx& c, const FeatLds& L, int a
 }
 
 // convert_global_state map: dst [4][H][W] (grid, robots, waiting starts, active targets)
-__device__ inline void emit_critic_map(const FeatCtx& c, const FeatLds& L, float* dst) {
+template <class T>
+__device__ inline void emit_critic_map(const FeatCtx& c, const FeatLds& L, T* dst) {
     const int HW = c.HW, NW = c.NW;
     const int lane = lane_id();
-    if ((HW & 3) == 0 && (((uintptr_t)dst) & 15) == 0) {
+    if constexpr (is_half_out<T>::value) {
+        if ((HW & 7) == 0 && (((uintptr_t)dst) & 15) == 0) {
+            const int qpp = HW >> 3;
+            const float inv_qpp = 1.0f / (float)qpp;
+            uint4* d4 = reinterpret_cast<uint4*>(dst);
+            for (int q = lane; q < 4 * qpp; q += WAVE) {
+                const int ch = fdivi(q, qpp, inv_qpp);
+                const int c0 = (q - ch * qpp) << 3;   // a multiple of 8: the 8 bits lie in one word
+                const int set = ch == 0 ? BS_GRID : ch == 1 ? BS_ROBOT : ch == 2 ? BS_WSTART : BS_ATARGET;
+                d4[q] = half8_of_bits<T>(L.bits[set * NW + (c0 >> 5)] >> (c0 & 31));
+            }
+            return;
+        }
+    } else if ((HW & 3) == 0 && (((uintptr_t)dst) & 15) == 0) {
         const int qpp = HW >> 2;
         const float inv_qpp = 1.0f / (float)qpp;
         float4* d4 = reinterpret_cast<float4*>(dst);
@@ -648,9 +793,9 @@ __device__ inline void actor_tuple(const Trk& trk, const FeatCtx& c, const FeatL
 }
 
 // generate_vector_features for agents [a0, a0+na): dst [na][6+5MO+5MP+1]
-template <class Trk>
+template <class Trk, class T>
 __device__ inline void emit_actor_vecs(const Trk& trk, const FeatCtx& c, const FeatLds& L, int a0, int na,
-                                       bool a_valid, float* dst) {
+                                       bool a_valid, T* dst) {
     const int lane = lane_id();
     const int Dv = 6 + 5 * c.MO + 5 * c.MP + 1;
     if (!a_valid) {
@@ -690,8 +835,8 @@ __device__ inline void emit_actor_vecs(const Trk& trk, const FeatCtx& c, const F
 }
 
 // convert_global_state vector: dst [6MR+7MPs+1] (MAPPO/helper.py:199-255)
-template <class Trk>
-__device__ inline void emit_critic_vec(const Trk& trk, const FeatCtx& c, const FeatLds& L, float* dst) {
+template <class Trk, class OT>
+__device__ inline void emit_critic_vec(const Trk& trk, const FeatCtx& c, const FeatLds& L, OT* dst) {
     const int lane = lane_id();
     const int H = c.H, W = c.W, t = c.t, T = c.T, MR = c.MR;
     const int Dg = 6 * MR + 7 * c.MPs + 1;

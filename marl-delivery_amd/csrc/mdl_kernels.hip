@@ -1325,6 +1325,7 @@ __device__ __forceinline__ auto staged_tracker(const ObsLdsPre& S, int P) {
     else return TrkFresh{S.pk, S.ps, P};
 }
 
+// (k_obs_h below restates this kernel's set-up, mask test and loads: change both.)
 template <bool STALE>
 __global__ __launch_bounds__(256) void k_obs(DevParams p, int env_begin, int n, float* __restrict__ amap,
                                              float* __restrict__ avec, float* __restrict__ cmap,
@@ -1390,6 +1391,73 @@ __global__ __launch_bounds__(256) void k_obs(DevParams p, int env_begin, int n, 
         if (cvec) {
             const int Dg = 6 * c.MR + 7 * c.MPs + 1;
             emit_critic_vec(trk, c, L, cvec + le * (size_t)Dg);
+        }
+    };
+    run(staged_tracker<STALE>(S, P));
+}
+
+// k_obs with half outputs (BF false fp16, true bfloat16; mdl_build_obs_as): the same staging, sorts and
+// vector emitters on the half element type, the maps through emit_actor_maps / emit_critic_map (eight
+// elements per lane where HW % 8 == 0; the plane words of the LDS slice stay unused).  A twin of
+// k_obs: the set-up and loads below restate k_obs's and must change with them.  They are not a
+// shared body because k_obs's machine code must stay what it is (scripts/isa_diff.py).
+template <bool STALE, bool BF>
+__global__ __launch_bounds__(256) void k_obs_h(DevParams p, int env_begin, int n,
+                                               typename half_out<BF>::type* __restrict__ amap,
+                                               typename half_out<BF>::type* __restrict__ avec,
+                                               typename half_out<BF>::type* __restrict__ cmap,
+                                               typename half_out<BF>::type* __restrict__ cvec, int wpb,
+                                               int lds_stride, const uint8_t* __restrict__ mask) {
+    typedef typename half_out<BF>::type H;
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int wave = wave_id();
+    const int lane = lane_id();
+    const int w = xcd_block() * wpb + wave;
+    if (wave >= wpb || w >= n) return;
+    if (mask && !mask[w]) return;   // row mask (mdl_step_episode): the row stays unwritten
+    const int e = env_begin + w;
+    const int A = p.A, P = p.P;
+    unsigned char* base = smem + (size_t)wave * lds_stride;
+    ObsLdsPre S = obs_pre_carve(base, P);
+    const MapDesc md = p.maps[p.env_map ? p.env_map[e] : 0];
+    FeatCtx c;
+    c.A = A; c.NS = P; c.H = md.H; c.W = md.W; c.HW = md.H * md.W; c.NW = (c.HW + 31) / 32;
+    c.t = p.es[e].t; c.T = p.obsT;
+    c.MO = p.MO; c.MP = p.MP; c.MR = p.MR; c.MPs = p.MPs;
+    c.MPc = p.MP < P ? p.MP : P;
+    c.MPsc = p.MPs < P ? p.MPs : P;
+    c.gridbits = p.gridbits + md.bits_off;
+    c.rank = p.rank + md.rank_off;
+    c.inv_hw = md.inv_hw;
+    FeatDims fd{A, P, c.HW, c.MPc, c.MPsc, stage_floats(A, A, c.MO, c.MPc, c.MR, c.MPsc)};
+    FeatLds L = feat_carve(base + obs_pre_bytes(P), fd);
+    const bool act = lane < A;
+    const uint32_t rv = act ? p.rob[(size_t)e * A + lane] : 0u;
+    const int cell = rob_cell(rv);
+    const int carry = rob_carry(rv);
+    stage_tracker<STALE>(p, e, P, lane, S);
+    auto run = [&](const auto& trk) {
+        feat_prepare(trk, c, L, cell, carry);
+        const size_t le = (size_t)w;
+        H* am = amap ? amap + le * (size_t)A * 6 * c.HW : nullptr;
+        H* cm = cmap ? cmap + le * 4 * (size_t)c.HW : nullptr;
+        // always_inline at the calls, not on the emitters (k_obs and k_views_* share them): an emitter
+        // out of line is a call, which puts c and L on the stack -- this kernel must have no scratch
+        if (am) [[clang::always_inline]] emit_actor_maps(c, L, 0, A, true, am);
+        if (cm) [[clang::always_inline]] emit_critic_map(c, L, cm);
+        if (avec) {
+            if (p.key32_dsh > 0 && P <= WAVE && A <= 8) {
+                for (int a = 0; a < A; a++) feat_sort_others(c, L, a, cell);
+                feat_sort_pkgs_fast<decltype(trk), 8>(trk, c, L, p.key32_dsh);
+            } else {
+                for (int a = 0; a < A; a++) feat_sort_agent(trk, c, L, a, cell);
+            }
+            const int Dv = 6 + 5 * c.MO + 5 * c.MP + 1;
+            [[clang::always_inline]] emit_actor_vecs(trk, c, L, 0, A, true, avec + le * (size_t)A * Dv);
+        }
+        if (cvec) {
+            const int Dg = 6 * c.MR + 7 * c.MPs + 1;
+            [[clang::always_inline]] emit_critic_vec(trk, c, L, cvec + le * (size_t)Dg);
         }
     };
     run(staged_tracker<STALE>(S, P));
@@ -2336,11 +2404,31 @@ hipError_t launch_views_idq_reward(const int32_t* prev, const int64_t* prev_offs
     return hipGetLastError();
 }
 
-hipError_t launch_obs(const DevParams& p, int env_begin, int n, float* amap, float* avec, float* cmap, float* cvec,
-                      int wpb, size_t lds, hipStream_t s, int rank_lds, const uint8_t* mask) {
+hipError_t launch_obs(const DevParams& p, int env_begin, int n, void* amap_, void* avec_, void* cmap_, void* cvec_,
+                      int wpb, size_t lds, hipStream_t s, int rank_lds, const uint8_t* mask, int dtype) {
+    if (dtype != OBS_F32 && dtype != OBS_F16 && dtype != OBS_BF16) return hipErrorInvalidValue;
     const dim3 g(blocks_for(n, wpb)), b(256);
     with_int<0, 1>(p.stale != 0, [&](auto st) {
         constexpr bool ST = decltype(st)::value != 0;
+        if (dtype != OBS_F32) {   // half outputs: the same builders and launch shape
+            with_int<OBS_F16, OBS_BF16>(dtype, [&](auto dt) {
+                constexpr bool BF = decltype(dt)::value == OBS_BF16;
+                typedef typename half_out<BF>::type H;
+                H *amap = (H*)amap_, *avec = (H*)avec_, *cmap = (H*)cmap_, *cvec = (H*)cvec_;
+                if (!p.obs_small) {
+                    hipLaunchKernelGGL((k_obs_h<ST, BF>), g, b, lds * wpb, s, p, env_begin, n, amap, avec, cmap, cvec,
+                                       wpb, (int)lds, mask);
+                    return;
+                }
+                with_int<0, 1>(rank_lds > 0, [&](auto rl) {
+                    hipLaunchKernelGGL((k_obs_small_h<ST, decltype(rl)::value != 0, BF>), g, b,
+                                       (size_t)rank_lds + lds * wpb, s, p, env_begin, n, amap, avec, cmap, cvec, wpb,
+                                       (int)lds, rank_lds, mask);
+                });
+            });
+            return;
+        }
+        float *amap = (float*)amap_, *avec = (float*)avec_, *cmap = (float*)cmap_, *cvec = (float*)cvec_;
         if (!p.obs_small) {
             hipLaunchKernelGGL(k_obs<ST>, g, b, lds * wpb, s, p, env_begin, n, amap, avec, cmap, cvec, wpb, (int)lds,
                                mask);

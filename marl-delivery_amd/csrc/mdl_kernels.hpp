@@ -55,9 +55,13 @@ hipError_t launch_episode_end(uint8_t* active, const uint8_t* filled, const uint
 // distance-rank table (mdl_obs_small.hpp k_obs_small).  PRECONDITION: envs [env_begin, env_begin+n)
 // share one map shape -- the table copied is env_begin's map's.  The engine checks it
 // (MdlEngine::launch_obs, mdl_engine.hip) before every call.  mask (device, [n], may be null):
-// row w is built only where mask[w] != 0, the other rows stay unwritten.
-hipError_t launch_obs(const DevParams& p, int env_begin, int n, float* amap, float* avec, float* cmap, float* cvec,
-                      int wpb, size_t lds, hipStream_t s, int rank_lds = 0, const uint8_t* mask = nullptr);
+// row w is built only where mask[w] != 0, the other rows stay unwritten.  dtype (OBS_F32 / F16 /
+// BF16): the four outputs' element type; the half types run k_obs_small_h / k_obs_h in the same
+// launch shape (anything else: hipErrorInvalidValue).
+enum : int { OBS_F32 = 0, OBS_F16 = 1, OBS_BF16 = 2 };   // = MDL_OBS_* (mdl_engine.h; checked in mdl_engine.hip)
+hipError_t launch_obs(const DevParams& p, int env_begin, int n, void* amap, void* avec, void* cmap, void* cvec,
+                      int wpb, size_t lds, hipStream_t s, int rank_lds = 0, const uint8_t* mask = nullptr,
+                      int dtype = 0);
 // A launch's own completion word (host-mapped): every wave of its grid counts itself in the
 // running device counter `ctr` (never reset: `base` is its value before the launch) after a
 // system-scope release of its stores; the last one writes `value` to `seq`.  seq == nullptr: none;

@@ -48,6 +48,23 @@ __device__ inline void zero_fill(float* dst, int n) {
     if (tail + lane < n) dst[tail + lane] = 0.0f;
 }
 
+// The same for half elements (f16_t / bf16_t), any 2-byte alignment: element head to 16-B
+// alignment (up to seven), 16-B body of eight zeros per lane per pass, element tail.
+template <class OT>
+__device__ inline void zero_fill(OT* dst, int n) {
+    static_assert(is_half_out<OT>::value, "zero_fill: float32 has its own");
+    if (n <= 0) return;
+    const int lane = lane_id();
+    int head = (int)(((16 - ((uintptr_t)dst & 15)) & 15) >> 1);
+    if (head > n) head = n;
+    if (lane < head) dst[lane] = OT{0};
+    const int nb = (n - head) >> 3;
+    uint4* d4 = reinterpret_cast<uint4*>(dst + head);
+    for (int q = lane; q < nb; q += WAVE) d4[q] = make_uint4(0u, 0u, 0u, 0u);
+    const int tail = head + 8 * nb;
+    if (tail + lane < n) dst[tail + lane] = OT{0};
+}
+
 // Flat bit image of np output planes of HW cells each: bit p*HW + cell of FB is
 // the value of (plane p, cell), so the planes are packed with no per-plane padding
 // and bit i is float i of the [np][H][W] output.  src(p, c0) returns the 32 bits
@@ -120,6 +137,18 @@ __device__ inline void emit_flat4(const uint32_t* FB, int n, float* dst) {
 // The same, one dword per lane (an unaligned destination).
 __device__ inline void emit_flat1(const uint32_t* FB, int n, float* dst) {
     for (int i = lane_id(); i < n; i += WAVE) dst[i] = ((FB[i >> 5] >> (i & 31)) & 1u) ? 1.0f : 0.0f;
+}
+
+// n half elements of a flat bit image at dst (any 2-byte alignment): eight elements, 16 B, per lane
+// per pass.  Element i is bit i; after a head of h elements the body's 8-bit groups start at bit
+// h + 8q, so a group may straddle two words: the word after the group's first is read with it (past
+// the image's last word that is the next array of the wave's LDS slice, and none of its bits is used).
+template <class OT>
+__device__ inline void emit_flat_h(const uint32_t* FB, int n, OT* dst) {
+    emit_bits_h(dst, n, [&](int i) -> uint32_t {
+        const uint32_t* w = FB + (i >> 5);
+        return __builtin_amdgcn_alignbit(w[1], w[0], (uint32_t)(i & 31));
+    });
 }
 
 // Lane-mask select with the mask in an SGPR pair: bit l set -> b, else a (one VALU op).
@@ -261,12 +290,17 @@ __host__ __device__ inline bool obs_small_ok(int A, int P, int key7_dsh, int max
 // step + observation kernel (k_step<..., OBS = true>) passes the step's registers.
 // `smem_wave` is this wave's LDS slice (obs_small_lds bytes).  rank_lds: the map's distance-rank
 // table already copied into the workgroup's LDS (k_obs_small), or null: read from global memory.
-template <bool STALE>
+// OT: the outputs' element type, float or a half type (f16_t / bf16_t, mdl_features.hpp): every value
+// is computed in float32 as for float outputs and rounded once (to nearest-even) where it is stored;
+// the maps' 0/1 elements come straight from the bit images.  Half actor vectors never take the
+// single-write image (its windows are in units of float4): they take the early fill, then the tuples.
+template <bool STALE, class OT = float>
 __device__ __forceinline__ void obs_small_emit(const DevParams& p, int w, int mi, uint32_t rv, uint64_t pkd,
-                                               uint32_t f, uint64_t tdd, int t, float* __restrict__ amap,
-                                               float* __restrict__ avec, float* __restrict__ cmap,
-                                               float* __restrict__ cvec, unsigned char* smem_wave,
+                                               uint32_t f, uint64_t tdd, int t, OT* __restrict__ amap,
+                                               OT* __restrict__ avec, OT* __restrict__ cmap,
+                                               OT* __restrict__ cvec, unsigned char* smem_wave,
                                                const uint16_t* rank_lds = nullptr) {
+    constexpr bool HALF = is_half_out<OT>::value;
     const int lane = lane_id();
     const int A = p.A, P = p.P;
     const MapDesc md = p.maps[mi];
@@ -303,7 +337,7 @@ __device__ __forceinline__ void obs_small_emit(const DevParams& p, int w, int mi
     // as one contiguous float4 stream, and the filled tuples are written over it
     // later, after an s_waitcnt vmcnt(0) (stores count in vmcnt on gfx9: the
     // zeros have reached L2 before any overwrite is issued).
-    const bool sw = avec && obs_sw_config(A, P, MO, MP) && (((uintptr_t)avec & 15) == 0);
+    const bool sw = !HALF && avec && obs_sw_config(A, P, MO, MP) && (((uintptr_t)avec & 15) == 0);
     const bool av_early = !sw && avec && (MO > MOc || MP > MPc);
     if (av_early) zero_fill(avec + (size_t)w * A * (6 + 5 * MO + 5 * MP + 1), A * (6 + 5 * MO + 5 * MP + 1));
 
@@ -373,8 +407,8 @@ __device__ __forceinline__ void obs_small_emit(const DevParams& p, int w, int mi
     wave_sync();
 
     // ---- maps ----
-    float* am = amap ? amap + (size_t)w * A * 6 * HW : nullptr;
-    float* cm = cmap ? cmap + (size_t)w * 4 * HW : nullptr;
+    OT* am = amap ? amap + (size_t)w * A * 6 * HW : nullptr;
+    OT* cm = cmap ? cmap + (size_t)w * 4 * HW : nullptr;
     if (am) {
         // plane p = (agent p/6, channel p%6): grid, self, other robots, waiting starts,
         // active targets, own carried target (MAPPO/helper.py:6-66)
@@ -390,19 +424,24 @@ __device__ __forceinline__ void obs_small_emit(const DevParams& p, int w, int mi
     if (cm)   // critic planes = bitsets 0..3 (grid, robots, waiting starts, active targets)
         build_flat(cplanes, 4, HW, [&](int pp, int c0) -> uint32_t { return bits_at(bits, NW, pp, c0); });
     wave_sync();
-    if (am) {
-        if (((uintptr_t)am & 15) == 0) emit_flat4(planes, 6 * A * HW, am);
-        else emit_flat1(planes, 6 * A * HW, am);
-    }
-    if (cm) {
-        if (((uintptr_t)cm & 15) == 0) emit_flat4(cplanes, 4 * HW, cm);
-        else emit_flat1(cplanes, 4 * HW, cm);
+    if constexpr (HALF) {
+        if (am) emit_flat_h(planes, 6 * A * HW, am);
+        if (cm) emit_flat_h(cplanes, 4 * HW, cm);
+    } else {
+        if (am) {
+            if (((uintptr_t)am & 15) == 0) emit_flat4(planes, 6 * A * HW, am);
+            else emit_flat1(planes, 6 * A * HW, am);
+        }
+        if (cm) {
+            if (((uintptr_t)cm & 15) == 0) emit_flat4(cplanes, 4 * HW, cm);
+            else emit_flat1(cplanes, 4 * HW, cm);
+        }
     }
 
     // ---- actor vectors (MAPPO/helper.py:68-165) ----
     if (avec) {
         const int Dv = 6 + 5 * MO + 5 * MP + 1;
-        float* av = avec + (size_t)w * A * Dv;
+        OT* av = avec + (size_t)w * A * Dv;
         // package order of each agent: (max(0,dl-t), distance rank, dict order) ascending
         const int np = popc64(ballot(wt));
         const int want = np < MPc ? np : MPc;
@@ -566,19 +605,32 @@ __device__ __forceinline__ void obs_small_emit(const DevParams& p, int w, int mi
             if ((ovalid && opos < MO) || (is_p && (phas || !sw)) || is_s) {
 #endif
                 const int off = is_s ? 0 : is_o ? 6 + 5 * opos : 6 + 5 * MO + 5 * qb;
-                float* o = sw ? img_at(is_p ? 2 * qa + 1 : 2 * qa, qa * Dv + off) : av + qa * Dv + off;
-                o[0] = d1;
-                o[1] = d2;
-                o[2] = is_p ? d3 : fl;
-                o[3] = is_p ? d4 : d3;
-                o[4] = is_p ? d5 : d4;
-                if (is_s) {
-                    o[5] = d5;
-                    if (!sw) o[Dv - 1] = qdiv_r(t, yT);   // yT = 0 when T <= 0
+                if constexpr (HALF) {
+                    OT* o = av + qa * Dv + off;
+                    o[0] = out_cvt<OT>(d1);
+                    o[1] = out_cvt<OT>(d2);
+                    o[2] = out_cvt<OT>(is_p ? d3 : fl);
+                    o[3] = out_cvt<OT>(is_p ? d4 : d3);
+                    o[4] = out_cvt<OT>(is_p ? d5 : d4);
+                    if (is_s) {
+                        o[5] = out_cvt<OT>(d5);
+                        o[Dv - 1] = out_cvt<OT>(qdiv_r(t, yT));
+                    }
+                } else {
+                    float* o = sw ? img_at(is_p ? 2 * qa + 1 : 2 * qa, qa * Dv + off) : av + qa * Dv + off;
+                    o[0] = d1;
+                    o[1] = d2;
+                    o[2] = is_p ? d3 : fl;
+                    o[3] = is_p ? d4 : d3;
+                    o[4] = is_p ? d5 : d4;
+                    if (is_s) {
+                        o[5] = d5;
+                        if (!sw) o[Dv - 1] = qdiv_r(t, yT);   // yT = 0 when T <= 0
+                    }
                 }
             }
         }
-        if (sw) {
+        if (sw) {   // (never with half outputs: dead code there)
             // Stream the slab once: every window's float4s from the image (a float4 that also holds
             // another env's floats -- only at the slab's ends -- per float), the gap up to the next
             // window as zeros.  The first window starts at the slab's first float4 and the last ends
@@ -596,7 +648,7 @@ __device__ __forceinline__ void obs_small_emit(const DevParams& p, int w, int mi
                 const int4 wt = wtab[wi];
                 const float4 v = img4[wt.z + (q - wt.x)];
                 const int f0 = 4 * q - g0;
-                float* d = avec + 4 * (size_t)q;
+                float* d = reinterpret_cast<float*>(avec) + 4 * (size_t)q;
                 if ((unsigned)f0 < (unsigned)S) d[0] = v.x;
                 if ((unsigned)(f0 + 1) < (unsigned)S) d[1] = v.y;
                 if ((unsigned)(f0 + 2) < (unsigned)S) d[2] = v.z;
@@ -627,7 +679,7 @@ __device__ __forceinline__ void obs_small_emit(const DevParams& p, int w, int mi
     // ---- critic vector (MAPPO/helper.py:199-255) ----
     if (cvec) {
         const int Dg = 6 * MR + 7 * MPs + 1;
-        float* cv = cvec + (size_t)w * Dg;
+        OT* cv = cvec + (size_t)w * Dg;
         const int nr = A < MR ? A : MR;
         const int npr = nact < MPsc ? nact : MPsc;
         for (int q0 = 0; q0 < nr + npr; q0 += WAVE) {   // uniform trip count: bperm needs every lane
@@ -652,25 +704,26 @@ __device__ __forceinline__ void obs_small_emit(const DevParams& p, int w, int mi
             const float d6 = hascar ? qdiv_r(p_car, yM) : -1.0f;   // yM = 0 when MR <= 1
             const float fl = isr ? (r_cy != 0 ? 1.0f : 0.0f) : (waiting ? 0.0f : 1.0f);
             if (live) {
-                float* o = cv + (isr ? 6 * q : 6 * MR + 7 * (q - nr));
-                o[0] = d1;
-                o[1] = d2;
-                o[2] = isr ? fl : d3;
-                o[3] = isr ? d3 : d4;
-                o[4] = isr ? d4 : d5;
-                o[5] = isr ? d5 : fl;
-                if (!isr) o[6] = d6;
+                OT* o = cv + (isr ? 6 * q : 6 * MR + 7 * (q - nr));
+                o[0] = out_cvt<OT>(d1);
+                o[1] = out_cvt<OT>(d2);
+                o[2] = out_cvt<OT>(isr ? fl : d3);
+                o[3] = out_cvt<OT>(isr ? d3 : d4);
+                o[4] = out_cvt<OT>(isr ? d4 : d5);
+                o[5] = out_cvt<OT>(isr ? d5 : fl);
+                if (!isr) o[6] = out_cvt<OT>(d6);
             }
         }
         zero_fill(cv + 6 * nr, 6 * (MR - nr));
         zero_fill(cv + 6 * MR + 7 * npr, 7 * (MPs - npr));
-        if (lane == 0) cv[Dg - 1] = qdiv_r(t, yT);
+        if (lane == 0) cv[Dg - 1] = out_cvt<OT>(qdiv_r(t, yT));
     }
 }
 
 // rank_lds > 0: the launch's maps (one shape, so one rank table) have their table copied into the
 // first rank_lds bytes of the workgroup's LDS before the waves start: the package-order keys and the
-// other-robot order then gather ranks from LDS (~64 cycles) instead of L2 (hundreds)
+// other-robot order then gather ranks from LDS (~64 cycles) instead of L2 (hundreds).
+// (k_obs_small_h below restates this kernel's table copy, mask test and loads: change both.)
 template <bool STALE, bool RL>
 __global__ __launch_bounds__(256) void k_obs_small(DevParams p, int env_begin, int n, float* __restrict__ amap,
                                                    float* __restrict__ avec, float* __restrict__ cmap,
@@ -706,6 +759,57 @@ __global__ __launch_bounds__(256) void k_obs_small(DevParams p, int env_begin, i
     const int t = p.es[e].t;
     obs_small_emit<STALE>(p, w, mi, rv, pkd, f, tdd, t, amap, avec, cmap, cvec,
                           smem + rank_lds + (size_t)wave * lds_stride, RL ? rk : nullptr);
+}
+
+// k_obs_small with half outputs: BF false fp16, true bfloat16 (mdl_build_obs_as).  A twin of k_obs_small:
+// the rank-table copy, the mask test and the loads below restate that kernel's and must change with
+// them.  They are not a shared body because k_obs_small's machine code must stay what it is
+// (scripts/isa_diff.py).
+template <bool BF>
+struct half_out {
+    typedef f16_t type;
+};
+template <>
+struct half_out<true> {
+    typedef bf16_t type;
+};
+template <bool STALE, bool RL, bool BF>
+__global__ __launch_bounds__(256) void k_obs_small_h(DevParams p, int env_begin, int n,
+                                                     typename half_out<BF>::type* __restrict__ amap,
+                                                     typename half_out<BF>::type* __restrict__ avec,
+                                                     typename half_out<BF>::type* __restrict__ cmap,
+                                                     typename half_out<BF>::type* __restrict__ cvec, int wpb,
+                                                     int lds_stride, int rank_lds, const uint8_t* __restrict__ mask) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int wave = wave_id();
+    const int lane = lane_id();
+    uint16_t* rk = (uint16_t*)smem;
+    if constexpr (RL) {
+        const MapDesc md0 = p.maps[p.env_map ? p.env_map[env_begin] : 0];   // every env of the launch: one shape
+        const int nrk = (2 * md0.H - 1) * (2 * md0.W - 1);
+        const uint16_t* src = p.rank + md0.rank_off;
+        for (int i = (int)threadIdx.x; i < nrk; i += 256) rk[i] = src[i];
+        __syncthreads();   // every wave of the block is still here (none has returned yet)
+    }
+    const int w = xcd_block() * wpb + wave;
+    if (wave >= wpb || w >= n) return;
+    if (mask && !mask[w]) return;   // row mask (mdl_step_episode): the row stays unwritten
+    const int e = env_begin + w;
+    const int A = p.A, P = p.P;
+    const int mi = p.env_map ? p.env_map[e] : 0;
+    // ---- loads: robots, packages (+ tracker data), clock ----
+    const uint32_t rv = lane < A ? p.rob[(size_t)e * A + lane] : 0u;
+    uint64_t pkd = 0, tdd = 0;
+    uint32_t f = 0;
+    if (lane < P) {
+        const size_t g = (size_t)e * P + lane;
+        pkd = p.pkg[g];
+        f = p.pstate[g];
+        if (STALE) tdd = p.trk[g];
+    }
+    const int t = p.es[e].t;
+    obs_small_emit<STALE, typename half_out<BF>::type>(p, w, mi, rv, pkd, f, tdd, t, amap, avec, cmap, cvec,
+                                                       smem + rank_lds + (size_t)wave * lds_stride, RL ? rk : nullptr);
 }
 
 }  // namespace mdl

@@ -33,6 +33,9 @@ MDL_MAX_PACKAGES = 1024
 MDL_REPLAY_MAX_ENVS = 65536
 MDL_OBS_BUILDER_AUTO = 0
 MDL_OBS_BUILDER_GENERIC = 1
+MDL_OBS_F32 = 0
+MDL_OBS_F16 = 1
+MDL_OBS_BF16 = 2
 MDL_STEP_LAYOUT_AUTO = 0
 MDL_STEP_LAYOUT_WAVE = 1
 MDL_STEP_LAYOUT_ROWS = 2
@@ -79,10 +82,12 @@ SIGNATURES = {
     "mdl_tracker_clear": (C.c_int, [_vp, _vp, _i32, _vp]),
     "mdl_step": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "mdl_step_obs": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mdl_step_obs_as": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "mdl_step_episode": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mdl_step_fused": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "mdl_step_floor": (C.c_int, [_vp, _i32, _vp]),
     "mdl_build_obs": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "mdl_build_obs_as": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "mdl_build_obs_alt": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp]),
     "mdl_alt_pre_bytes": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
     "mdl_alt_transition": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),

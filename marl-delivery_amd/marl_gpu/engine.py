@@ -39,7 +39,16 @@ STEP_LAYOUTS = {"auto": _lib.MDL_STEP_LAYOUT_AUTO, "wave": _lib.MDL_STEP_LAYOUT_
 _LAYOUT_NAMES = {_lib.MDL_STEP_LAYOUT_WAVE: "wave", _lib.MDL_STEP_LAYOUT_ROWS: "rows", _lib.MDL_STEP_LAYOUT_HALVES: "halves"}
 STATUS_NAMES = ("None", "waiting", "in_transit", "delivered")
 OBS_KEYS = ("actor_map", "actor_vec", "critic_map", "critic_vec")
+# element types of the MAPPO/QMIX observation tensors (build_obs / step_obs): float32, or the float32
+# value rounded once to nearest-even (bit for bit ``x.to(dtype)``)
+OBS_DTYPES = {torch.float32: _lib.MDL_OBS_F32, torch.float16: _lib.MDL_OBS_F16, torch.bfloat16: _lib.MDL_OBS_BF16}
 ALT_KEYS = ("idq_obs", "qmix_state")
+
+
+def _obs_dtype(dtype):
+    if dtype not in OBS_DTYPES:
+        raise TypeError(f"observation dtype must be torch.float32, torch.float16 or torch.bfloat16, not {dtype}")
+    return OBS_DTYPES[dtype]
 
 
 def _as_grid(m):
@@ -284,13 +293,19 @@ class BatchedEnv:
         return out[0], out[1], out[2]
 
     def step_obs(self, actions: torch.Tensor, auto_reset: bool = True, action_format: str = "int", out=None,
-                 obs_out: dict | None = None, which=("actor_map", "actor_vec", "critic_map", "critic_vec")):
+                 obs_out: dict | None = None, which=("actor_map", "actor_vec", "critic_map", "critic_vec"),
+                 obs_dtype: torch.dtype = torch.float32):
         """``step`` over all envs, then ``build_obs`` of the new state (the trainer's per-step
         sequence, MAPPO/trainer.py:229-286), as one launch when A <= 8 and P <= 64: the
         kernel builds the observations from the state the step leaves in registers.
         Bit-identical to ``step(...)`` followed by ``build_obs()``.  The envs must share one
         map shape.  Returns (r_env, r_shaped, done, obs dict); without ``obs_out`` the obs
-        tensors are the engine's own buffers, overwritten by the next call."""
+        tensors are the engine's own buffers, overwritten by the next call.
+
+        ``obs_dtype``: the observation tensors' element type, as ``build_obs(dtype=)``.  With
+        torch.float16 / torch.bfloat16 the call is always the step launch followed by the builder's
+        (the fused kernel writes float32 only); rewards, done and the engine's state are the same."""
+        dt = _obs_dtype(obs_dtype)
         n = self.E
         if actions.dtype is not torch.uint8 or not actions.is_cuda or not actions.is_contiguous() \
                 or actions.get_device() != self._dev or actions.numel() != n * self.A:
@@ -303,9 +318,15 @@ class BatchedEnv:
         if self._shape_run_end[0] < n:
             raise ValueError("step_obs: the envs mix map shapes; use step() and build_obs() per same-shape group")
         H, W = self.grids[int(self.env_map[0])].shape
-        obs_out, op = self._obs_out(obs_out, which, n, H, W)
-        check(lib().mdl_step_obs(self._h, actions.data_ptr(), ACTION_FORMATS[action_format], 1 if auto_reset else 0,
-                                 ptrs[0], ptrs[1], ptrs[2], *op, _raw_stream(self._dev)), "mdl_step_obs")
+        obs_out, op = self._obs_out(obs_out, which, n, H, W, dtype=obs_dtype)
+        if dt == _lib.MDL_OBS_F32:
+            check(lib().mdl_step_obs(self._h, actions.data_ptr(), ACTION_FORMATS[action_format],
+                                     1 if auto_reset else 0, ptrs[0], ptrs[1], ptrs[2], *op, _raw_stream(self._dev)),
+                  "mdl_step_obs")
+        else:
+            check(lib().mdl_step_obs_as(self._h, actions.data_ptr(), ACTION_FORMATS[action_format],
+                                        1 if auto_reset else 0, ptrs[0], ptrs[1], ptrs[2], dt, *op,
+                                        _raw_stream(self._dev)), "mdl_step_obs_as")
         self._keep = (None, actions)
         # only the outputs written by this call (a cached dict's other entries would be stale)
         return out[0], out[1], out[2], {k: (v if k in which else None) for k, v in obs_out.items()}
@@ -422,11 +443,14 @@ class BatchedEnv:
         n = self.E if n is None else int(n)
         check(lib().mdl_step_floor(self._h, n, _raw_stream(self._dev)), "mdl_step_floor")
 
-    def obs_buffers(self, n=None, H=None, W=None):
+    def obs_buffers(self, n=None, H=None, W=None, dtype: torch.dtype = torch.float32):
+        """New observation tensors for n envs of an [H, W] map, of element type ``dtype``
+        (torch.float32, torch.float16 or torch.bfloat16: what ``build_obs`` / ``step_obs`` write)."""
+        _obs_dtype(dtype)
         n = self.E if n is None else n
         H = self.grids[0].shape[0] if H is None else H
         W = self.grids[0].shape[1] if W is None else W
-        f = dict(dtype=torch.float32, device=self.device)
+        f = dict(dtype=dtype, device=self.device)
         return dict(actor_map=torch.empty((n, self.A, 6, H, W), **f),
                     actor_vec=torch.empty((n, self.A, self.actor_vec_dim), **f),
                     critic_map=torch.empty((n, 4, H, W), **f),
@@ -445,32 +469,36 @@ class BatchedEnv:
                              f"same-shape group (this one ends at env {int(self._shape_run_end[env_begin])})")
         return n, self.grids[int(self.env_map[env_begin])]
 
-    def _check_obs_out(self, t, name, shape):
+    def _check_obs_out(self, t, name, shape, dtype=torch.float32):
         want = 1
         for s in shape:
             want *= s
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
-            raise TypeError(f"{name} must be a contiguous float32 device tensor")
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_cuda or not t.is_contiguous():
+            raise TypeError(f"{name} must be a contiguous {str(dtype).replace('torch.', '')} device tensor")
         if t.get_device() != self.device.index:
             raise ValueError(f"{name} must be on {self.device}, not cuda:{t.get_device()}")
         if t.numel() < want:
             raise ValueError(f"{name} holds {t.numel()} floats, needs {want} {tuple(shape)}")
 
-    def _obs_out(self, obs_out, which, n, H, W, strict=False):
+    def _obs_out(self, obs_out, which, n, H, W, strict=False, dtype=torch.float32):
         """The observation outputs of one call over n envs of an [H, W] map -> (the dict, the four
-        addresses in ``OBS_KEYS`` order).  Without ``obs_out`` the engine's own cached buffers.  Only
-        the entries ``which`` names are written (the others: address None), each checked against its
-        shape; ``strict``: a named entry must be in the dict."""
+        addresses in ``OBS_KEYS`` order).  Without ``obs_out`` the engine's own cached buffers (one set
+        per ``dtype``).  Only the entries ``which`` names are written (the others: address None), each
+        checked against its shape and ``dtype``; ``strict``: a named entry must be in the dict."""
         if obs_out is None:
-            obs_out = self._obs_cache if getattr(self, "_obs_cache", None) is not None else self.obs_buffers(n, H, W)
-            self._obs_cache = obs_out
+            cache = getattr(self, "_obs_cache", None)
+            if cache is None:
+                cache = self._obs_cache = {}
+            obs_out = cache.get(dtype)
+            if obs_out is None:
+                obs_out = cache[dtype] = self.obs_buffers(n, H, W, dtype)
         shapes = dict(actor_map=(n, self.A, 6, H, W), actor_vec=(n, self.A, self.actor_vec_dim),
                       critic_map=(n, 4, H, W), critic_vec=(n, self.critic_vec_dim))
         op = []
         for k in OBS_KEYS:
             t = (obs_out[k] if strict else obs_out.get(k)) if k in which else None
             if t is not None:
-                self._check_obs_out(t, k, shapes[k])
+                self._check_obs_out(t, k, shapes[k], dtype)
             op.append(ptr(t))
         return obs_out, op
 
@@ -492,16 +520,28 @@ class BatchedEnv:
         return out, op + [oh, ow]
 
     def build_obs(self, env_begin: int = 0, n: int | None = None, out: dict | None = None,
-                  which=("actor_map", "actor_vec", "critic_map", "critic_vec")):
+                  which=("actor_map", "actor_vec", "critic_map", "critic_vec"),
+                  dtype: torch.dtype = torch.float32):
         """convert_observation / generate_vector_features / convert_global_state
         for every agent of envs [env_begin, env_begin+n) (one map shape: raises
-        on a range that mixes map shapes)."""
+        on a range that mixes map shapes).
+
+        ``dtype``: the tensors' element type.  torch.float16 / torch.bfloat16 tensors hold the float32
+        values rounded once to nearest-even -- bit for bit ``build_obs()[k].to(dtype)`` -- written as
+        half elements by the builder itself (half the bytes: for a policy under autocast, or smaller
+        rollout buffers).  ``out`` tensors must have that dtype.  (``step_episode``, the evaluator, the
+        QMIX collectors and the IDQ / qmix featurizers stay float32.)"""
+        dt = _obs_dtype(dtype)
         n, g = self._obs_range(env_begin, n)
         H, W = g.shape
-        out, op = self._obs_out(self.obs_buffers(n, H, W) if out is None else out, which, n, H, W, strict=True)
+        out, op = self._obs_out(self.obs_buffers(n, H, W, dtype) if out is None else out, which, n, H, W,
+                                strict=True, dtype=dtype)
         if n == 0:
             return out
-        check(lib().mdl_build_obs(self._h, env_begin, n, *op, self._stream()), "mdl_build_obs")
+        if dt == _lib.MDL_OBS_F32:
+            check(lib().mdl_build_obs(self._h, env_begin, n, *op, self._stream()), "mdl_build_obs")
+        else:
+            check(lib().mdl_build_obs_as(self._h, env_begin, n, dt, *op, self._stream()), "mdl_build_obs_as")
         return out
 
     # ---- IDQ / qmix featurizers (SURVEY.md §8(f)2) ----

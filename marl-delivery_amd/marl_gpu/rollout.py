@@ -55,11 +55,21 @@ class MappoRollout(Graphed):
     the softmax over the available actions), and the masks are kept in ``mb_avail`` uint8
     [T, E, A, 15] so a learner applies the same mask when it recomputes log-probs.  The returned batch
     is unchanged in form.  avail=False (the default): nothing changes.
+
+    obs_dtype: the element type of the observation buffers (``mb_obs``, ``mb_vector_obs``,
+    ``mb_global_states``, ``mb_global_vector`` and ``next_obs``): torch.float32 (the default), or
+    torch.float16 / torch.bfloat16 -- the engine then writes the float32 observations rounded once to
+    nearest-even (``BatchedEnv.build_obs(dtype=)``), half the bytes, and actor and critic receive
+    tensors of that type (a policy under autocast, or one that casts its inputs).  Rewards, values,
+    log-probs, advantages and returns stay float32.
     """
 
     def __init__(self, env, rollout_steps: int, seed: int = 0, gamma: float = 0.99, gae_lambda: float = 0.95,
-                 avail: bool = False):
+                 avail: bool = False, obs_dtype: torch.dtype = torch.float32):
         self.env = env
+        if obs_dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise TypeError(f"obs_dtype must be torch.float32, torch.float16 or torch.bfloat16, not {obs_dtype}")
+        self.obs_dtype = obs_dtype
         self.T = int(rollout_steps)
         self.seed = int(seed)
         self._init_graphs(env.device)
@@ -69,16 +79,17 @@ class MappoRollout(Graphed):
         dev = env.device
         f = dict(dtype=torch.float32, device=dev)
         T = self.T
-        self.mb_obs = torch.zeros((T, E, A, 6, H, W), **f)
-        self.mb_vector_obs = torch.zeros((T, E, A, env.actor_vec_dim), **f)
-        self.mb_global_states = torch.zeros((T, E, 4, H, W), **f)
-        self.mb_global_vector = torch.zeros((T, E, env.critic_vec_dim), **f)
+        o = dict(dtype=obs_dtype, device=dev)
+        self.mb_obs = torch.zeros((T, E, A, 6, H, W), **o)
+        self.mb_vector_obs = torch.zeros((T, E, A, env.actor_vec_dim), **o)
+        self.mb_global_states = torch.zeros((T, E, 4, H, W), **o)
+        self.mb_global_vector = torch.zeros((T, E, env.critic_vec_dim), **o)
         self.mb_actions = torch.zeros((T, E, A), dtype=torch.uint8, device=dev)
         self.mb_log_probs = torch.zeros((T, E, A), **f)
         self.mb_rewards = torch.zeros((T, E), **f)
         self.mb_dones = torch.zeros((T, E), dtype=torch.uint8, device=dev)
         self.mb_values = torch.zeros((T, E), **f)
-        self.next_obs = env.obs_buffers(E, H, W)
+        self.next_obs = env.obs_buffers(E, H, W, obs_dtype)
         self._r_env = torch.zeros(E, dtype=torch.float64, device=dev)
         self._graph_out = None
         self.mb_avail = torch.ones((T, E, A, ACTION_DIM), dtype=torch.uint8, device=dev) if avail else None
@@ -111,7 +122,7 @@ class MappoRollout(Graphed):
     def _run(self, actor, critic, dev_offset: bool):
         env, T = self.env, self.T
         E, A = env.E, env.A
-        env.build_obs(out=self._slot(0))              # current obs = f(current state, tracker)
+        env.build_obs(out=self._slot(0), dtype=self.obs_dtype)   # current obs = f(current state, tracker)
         for step in range(T):
             obs = self.mb_obs[step]
             logits = actor(obs.reshape(E * A, *obs.shape[2:]), self.mb_vector_obs[step].reshape(E * A, -1))
@@ -126,7 +137,8 @@ class MappoRollout(Graphed):
             # step + the next observations in one launch (MAPPO/trainer.py:229-286)
             env.step_obs(self.mb_actions[step], auto_reset=True,
                          out=(self._r_env, self.mb_rewards[step], self.mb_dones[step]),
-                         obs_out=self._slot(step + 1) if step + 1 < T else self.next_obs)
+                         obs_out=self._slot(step + 1) if step + 1 < T else self.next_obs,
+                         obs_dtype=self.obs_dtype)
         if dev_offset:
             check(lib().mdl_counter_add(ptr(self._off_dev), T, stream_handle(env.device)), "mdl_counter_add")
         next_value = critic(self.next_obs["critic_map"], self.next_obs["critic_vec"]).reshape(E)

@@ -8,6 +8,8 @@
   --config 5   synthetic 64x64, A=16, P=100, E=131072/8 per GPU, step; full observations per
                chunk of 4096 envs (MDL_OBS_CHUNK)
   --config rollout / rollout_graph   MAPPO rollout on the device
+  --obs-dtype       float16 / bfloat16 observations: configs 3 / 3b time step_obs and build_obs for float32
+                    and the half types in one process; rollout / rollout_graph collect in that type
   --config alt      IDQ/qmix featurizers (§8(f)2)
   --config greedy   batched greedy baseline (§8(f)3)
   --qmix            QMIX episode collection: the masked step against the full step, and one collector
@@ -173,7 +175,64 @@ def run(cfg, steps, warmup):
     env.close()
 
 
-def run_rollout(steps, graph=False):
+OBS_DTYPES = {"float32": torch.float32, "float16": torch.float16, "bfloat16": torch.bfloat16}
+
+
+def run_obs_dtype(cfg, steps, warmup, names, rounds=3):
+    """Config 3 / 3b with half-precision observations ("Half-precision observations"):
+    in one process, on one engine, ``step_obs`` and ``build_obs`` alone for float32 and for each
+    half type of ``names`` -- the config 3 leg's warm-up and its hipGraph-replayed timed region (10
+    captured calls), each graph captured once and the types replayed in turn, ``rounds`` times.
+    float32 ``step_obs`` is the fused kernel; a half ``step_obs`` is the step launch + the builder's."""
+    import marl_gpu
+    from marl_gpu.maps import grid_array, load_map, map_path
+    dev = torch.device("cuda", 0)
+    E, A, P, T = 16384, 5, 50, 500
+    mo, mp = (4, 5) if cfg == "3" else (100, 100)
+    env = marl_gpu.BatchedEnv(grid_array(load_map(map_path("map1.txt"))), E, A, P, T, seed=42, tracker="mappo",
+                              max_other_robots=mo, max_packages_obs=mp)
+    env.reset()
+    gen = torch.Generator(device=dev).manual_seed(0)
+    G, C = 50, 10
+    acts = torch.randint(0, 15, (G, E, A), generator=gen, device=dev, dtype=torch.int32).to(torch.uint8)
+    for k in range(warmup):
+        env.step(acts[k % G])
+    r = torch.zeros(E, dtype=torch.float64, device=dev)
+    sh = torch.zeros(E, dtype=torch.float32, device=dev)
+    dn = torch.zeros(E, dtype=torch.uint8, device=dev)
+    names = ["float32"] + [n for n in names if n != "float32"]
+    elems = E * (A * 6 * 100 + A * env.actor_vec_dim + 4 * 100 + env.critic_vec_dim)
+    graphs = {}
+    for n in names:
+        dt = OBS_DTYPES[n]
+        bufs = env.obs_buffers(dtype=dt)
+
+        def steps_(bufs=bufs, dt=dt):
+            for k in range(C):
+                env.step_obs(acts[k % G], out=(r, sh, dn), obs_out=bufs, obs_dtype=dt)
+
+        def builds_(bufs=bufs, dt=dt):
+            for k in range(C):
+                env.build_obs(out=bufs, dtype=dt)
+
+        graphs[n] = (_graph_of(steps_), _graph_of(builds_), bufs)
+    reps = max(1, steps // 50)
+    res = {n: {"step_obs_us": [], "build_obs_us": []} for n in names}
+    for _ in range(rounds):
+        for n in names:
+            res[n]["step_obs_us"].append(_replay_us(graphs[n][0], reps, C))
+            res[n]["build_obs_us"].append(_replay_us(graphs[n][1], reps, C))
+    for n in names:
+        b = elems * (4 if n == "float32" else 2)
+        best = min(res[n]["build_obs_us"])
+        res[n].update(obs_write_bytes=b, step_obs_launches=1 if n == "float32" else 2,
+                      build_obs_roofline_frac=b / (best * 1e-6) / 1e9 / HBM)
+    print(json.dumps({"config": cfg + ":obs_dtype", "envs": E, "agents": A, "packages": P, "rounds": rounds,
+                      "replays": reps, "calls_per_graph": C, "dtypes": res}), flush=True)
+    env.close()
+
+
+def run_rollout(steps, graph=False, obs_dtype="float32"):
     """MAPPO rollout on the device: 4096 envs, map1, A=5, the
     trainer's featurizer sizes, a linear actor on the 52-dim vector and a linear
     critic on the 1301-dim vector; sampling, step, obs into the buffers and GAE
@@ -188,10 +247,11 @@ def run_rollout(steps, graph=False):
     g = torch.Generator(device="cuda").manual_seed(0)
     wa = torch.randn(env.actor_vec_dim, 15, device="cuda", generator=g) * 0.1
     wc = torch.randn(env.critic_vec_dim, device="cuda", generator=g) * 0.01
-    actor = lambda obs, vec: vec @ wa  # noqa: E731
-    critic = lambda gmap, gvec: gvec @ wc  # noqa: E731
+    actor = lambda obs, vec: vec.float() @ wa  # noqa: E731  (float(): the identity on float32 observations)
+    critic = lambda gmap, gvec: gvec.float() @ wc  # noqa: E731
     Tr = 128
-    ro = R.MappoRollout(env, Tr, seed=1)
+    ro = R.MappoRollout(env, Tr, seed=1) if obs_dtype == "float32" \
+        else R.MappoRollout(env, Tr, seed=1, obs_dtype=OBS_DTYPES[obs_dtype])
     ro.collect(actor, critic, graph=graph)   # (graph: this call runs eagerly and captures)
     torch.cuda.synchronize()
     n = max(1, steps // Tr)
@@ -201,6 +261,7 @@ def run_rollout(steps, graph=False):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     out = {"config": "rollout_graph" if graph else "rollout", "envs": E, "agents": A, "rollout_steps": Tr, "rollouts": n,
+           "obs_dtype": obs_dtype,
            "us_per_env_step": dt / (n * Tr) * 1e6, "agent_steps_per_s": E * A * n * Tr / dt,
            "note": "MappoRollout.collect: linear actor/critic (torch), on-device sampling, mdl_step_obs (step + "
                    "next observations in one launch) into the rollout buffers, GAE kernel"}
@@ -1020,7 +1081,15 @@ def main():
     ap.add_argument("--avail", action="store_true", help="the valid-action mask measurements only")
     ap.add_argument("--avail-collect", default="both", choices=["both", "off"],
                     help="with --avail: off = the QMIX collect without the option alone")
+    ap.add_argument("--obs-dtype", default="float32",
+                    help="float32, float16 or bfloat16 (or several, comma-separated): with a half type, configs 3 / 3b "
+                         "print the float32-against-half comparison of one process instead of their usual line, and "
+                         "rollout / rollout_graph collect into buffers of that type")
     a = ap.parse_args()
+    obs_dtypes = a.obs_dtype.split(",")
+    if any(n not in OBS_DTYPES for n in obs_dtypes):
+        ap.error(f"--obs-dtype: {a.obs_dtype!r} (float32, float16, bfloat16)")
+    half = [n for n in obs_dtypes if n != "float32"]
     torch.cuda.set_device(0)
     if a.avail:
         run_avail(a.steps, a.avail_collect)
@@ -1041,11 +1110,14 @@ def main():
         if c == "1":
             run_config1()
         elif c in ("rollout", "rollout_graph"):
-            run_rollout(a.steps, graph=c == "rollout_graph")
+            for n in obs_dtypes:
+                run_rollout(a.steps, graph=c == "rollout_graph", obs_dtype=n)
         elif c == "alt":
             run_alt(a.steps)
         elif c == "greedy":
             run_greedy(a.steps)
+        elif c in ("3", "3b") and half:
+            run_obs_dtype(c, a.steps, a.warmup, half)
         else:
             run(c, a.steps, a.warmup)
 
