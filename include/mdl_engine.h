@@ -170,7 +170,8 @@ int mdl_step_floor(MdlEngine* eng, int32_t n, void* stream);
  *                                        with state_tensor_shape (7, out_h, out_w); the trainers pass (7, H, W)
  * Either pointer may be NULL.  The IDQ / qmix trainers clear their tracker per episode: build the
  * engine with MDL_TRACKER_FRESH for them.
- * mdl_views_alt_features: the same on packed dict views (as mdl_views_features).
+ * mdl_views_alt_features: the same on packed dict views (as mdl_views_features: one map shape per
+ * call, records not validated -- see there).
  * mdl_views_idq_reward: reward_shaping (IDQ/networks.py:228-349) per agent, fp64, out[op_offsets[w]+a];
  * ops_are_ints = 0 reproduces IDQ/trainer.py, which passes string ops (so no op branch fires). */
 int mdl_build_obs_alt(MdlEngine* eng, int32_t env_begin, int32_t n, float* idq_obs, float* qmix_state, int32_t out_h,
@@ -536,7 +537,21 @@ int mdl_read_state(MdlEngine* eng, int32_t* robots, int32_t* pkgs, int32_t* t, d
  * early-return outputs).  Outputs per view: obs [6][H][W], vec [6+5MO+5MP+1],
  * gmap [4][H][W], gvec [6MR+7MPs+1] (NULL to skip).  T/MO/MP/MR/MPs are call
  * arguments here.  Replaces convert_observation / generate_vector_features /
- * convert_global_state called on dicts (MAPPO/helper.py:6-255). */
+ * convert_global_state called on dicts (MAPPO/helper.py:6-255).
+ *
+ * One map shape per call: all views of one mdl_views_features (or
+ * mdl_host_views_features, mdl_views_alt_features) call must name maps of the
+ * same (H, W); the maps themselves may differ.  Row w of obs, gmap and idq_obs
+ * starts at w * rows * H * W of the view's own map (rows = 6, 4, 6), so views
+ * of different shapes in one call would write overlapping rows.  Views of
+ * several shapes go into one call per shape.  mdl_views_shaped_reward and
+ * mdl_views_idq_reward have no per-shape output and may mix shapes freely.
+ *
+ * View records are NOT validated: they live on the device (or in the arena)
+ * and the library never reads them on the host.  A map index outside the
+ * engine's maps, a cell outside the view's map, n_slots > max_slots, A >
+ * MDL_MAX_ROBOTS or an offset outside the blob makes the kernel read or
+ * write out of bounds.  The caller guarantees all of these. */
 int mdl_views_features(MdlEngine* eng, const int32_t* views, const int64_t* offsets, int32_t n_views,
                        int32_t max_slots, const int32_t* agent_idx, int32_t T, int32_t MO, int32_t MP, int32_t MR, int32_t MPs,
                        float* obs, float* vec, float* gmap, float* gvec, void* stream);
