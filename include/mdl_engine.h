@@ -589,6 +589,12 @@ int mdl_last_step_layout(const MdlEngine* eng, int32_t* layout);
  * launches in `layout` (WAVE / ROWS / HALVES), or, with with_obs, of mdl_step_obs's step launch (its fused
  * step + observation kernel where it applies).  NUL-terminated into out[cap]. */
 int mdl_step_kernel_name(const MdlEngine* eng, int32_t layout, int32_t with_obs, char* out, int32_t cap);
+/* The symbol (as rocprof reports it, e.g. "mdl::k_obs_small<true, false>") of the observation builder
+ * mdl_build_obs (dtype = MDL_OBS_F32) or mdl_build_obs_as (MDL_OBS_F16 / _BF16) launches: the small
+ * builder k_obs_small<ST, RL> / k_obs_small_h<ST, RL, BF> (RL: the distance-rank table staged in LDS)
+ * or the general one, k_obs<ST> / k_obs_h<ST, BF>; ST: the stale tracker.  It comes from the selection
+ * the builder launch itself runs.  NUL-terminated into out[cap]. */
+int mdl_obs_kernel_name(const MdlEngine* eng, int32_t dtype, char* out, int32_t cap);
 int mdl_obs_dims(const MdlEngine* eng, int32_t* actor_vec_dim, int32_t* critic_vec_dim);
 const char* mdl_last_error(void);
 const char* mdl_version(void);

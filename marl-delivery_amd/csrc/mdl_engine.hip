@@ -1398,6 +1398,15 @@ int mdl_step_layout(const MdlEngine* eng, int32_t n, int32_t use_ids, int32_t* l
     return 0;
 }
 
+int mdl_obs_kernel_name(const MdlEngine* eng, int32_t dtype, char* out, int32_t cap) {
+    if (!eng || !out || cap < 1) return fail("mdl_obs_kernel_name: bad argument");
+    if (!obs_dtype_ok(dtype))
+        return fail("mdl_obs_kernel_name: unknown observation dtype %d (MDL_OBS_F32 / F16 / BF16)", dtype);
+    const int k = mdl::obs_kernel_name(eng->p, eng->obs_rank_lds, dtype, out, cap);
+    if (k < 0 || k >= cap) return fail("mdl_obs_kernel_name: buffer of %d bytes too small", cap);
+    return 0;
+}
+
 int mdl_step_kernel_name(const MdlEngine* eng, int32_t layout, int32_t with_obs, char* out, int32_t cap) {
     if (!eng || !out || cap < 1) return fail("mdl_step_kernel_name: bad argument");
     if (layout != MDL_STEP_LAYOUT_WAVE && layout != MDL_STEP_LAYOUT_ROWS && layout != MDL_STEP_LAYOUT_HALVES)

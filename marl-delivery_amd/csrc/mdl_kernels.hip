@@ -2404,40 +2404,74 @@ hipError_t launch_views_idq_reward(const int32_t* prev, const int64_t* prev_offs
     return hipGetLastError();
 }
 
-hipError_t launch_obs(const DevParams& p, int env_begin, int n, void* amap_, void* avec_, void* cmap_, void* cvec_,
-                      int wpb, size_t lds, hipStream_t s, int rank_lds, const uint8_t* mask, int dtype) {
-    if (dtype != OBS_F32 && dtype != OBS_F16 && dtype != OBS_BF16) return hipErrorInvalidValue;
-    const dim3 g(blocks_for(n, wpb)), b(256);
+// ---- the observation launches: one kernel selection (select_obs), as select_step for the steps ----
+template <class K>
+struct obs_kernel_out;   // a builder kernel's output element type: its first output pointer's
+template <class OT, class... R>
+struct obs_kernel_out<void (*)(DevParams, int, int, OT*, R...)> {
+    typedef OT type;
+};
+
+// The builder a launch runs for outputs of `dtype` (checked by the caller): calls
+// f(small, kernel, fmt, args...) with small (a std::integral_constant<bool>) telling which argument
+// list the kernel takes, the instantiation, and its symbol as rocprof names it -- a printf format
+// and its arguments.  Every rule of the dispatch lives here and nowhere else.
+template <class F>
+static void select_obs(const DevParams& p, int rank_lds, int dtype, F&& f) {
+    typedef std::integral_constant<bool, true> Small;
+    typedef std::integral_constant<bool, false> General;
     with_int<0, 1>(p.stale != 0, [&](auto st) {
         constexpr bool ST = decltype(st)::value != 0;
+        const char* const st_s = ST ? "true" : "false";
         if (dtype != OBS_F32) {   // half outputs: the same builders and launch shape
             with_int<OBS_F16, OBS_BF16>(dtype, [&](auto dt) {
                 constexpr bool BF = decltype(dt)::value == OBS_BF16;
-                typedef typename half_out<BF>::type H;
-                H *amap = (H*)amap_, *avec = (H*)avec_, *cmap = (H*)cmap_, *cvec = (H*)cvec_;
+                const char* const bf_s = BF ? "true" : "false";
                 if (!p.obs_small) {
-                    hipLaunchKernelGGL((k_obs_h<ST, BF>), g, b, lds * wpb, s, p, env_begin, n, amap, avec, cmap, cvec,
-                                       wpb, (int)lds, mask);
+                    f(General{}, k_obs_h<ST, BF>, "mdl::k_obs_h<%s, %s>", st_s, bf_s);
                     return;
                 }
                 with_int<0, 1>(rank_lds > 0, [&](auto rl) {
-                    hipLaunchKernelGGL((k_obs_small_h<ST, decltype(rl)::value != 0, BF>), g, b,
-                                       (size_t)rank_lds + lds * wpb, s, p, env_begin, n, amap, avec, cmap, cvec, wpb,
-                                       (int)lds, rank_lds, mask);
+                    constexpr bool RL = decltype(rl)::value != 0;
+                    f(Small{}, k_obs_small_h<ST, RL, BF>, "mdl::k_obs_small_h<%s, %s, %s>", st_s,
+                      RL ? "true" : "false", bf_s);
                 });
             });
             return;
         }
-        float *amap = (float*)amap_, *avec = (float*)avec_, *cmap = (float*)cmap_, *cvec = (float*)cvec_;
         if (!p.obs_small) {
-            hipLaunchKernelGGL(k_obs<ST>, g, b, lds * wpb, s, p, env_begin, n, amap, avec, cmap, cvec, wpb, (int)lds,
-                               mask);
+            f(General{}, k_obs<ST>, "mdl::k_obs<%s>", st_s);
             return;
         }
         with_int<0, 1>(rank_lds > 0, [&](auto rl) {   // the rank table staged in LDS, ahead of the waves' slices
-            hipLaunchKernelGGL((k_obs_small<ST, decltype(rl)::value != 0>), g, b, (size_t)rank_lds + lds * wpb, s, p,
-                               env_begin, n, amap, avec, cmap, cvec, wpb, (int)lds, rank_lds, mask);
+            constexpr bool RL = decltype(rl)::value != 0;
+            f(Small{}, k_obs_small<ST, RL>, "mdl::k_obs_small<%s, %s>", st_s, RL ? "true" : "false");
         });
+    });
+}
+
+int obs_kernel_name(const DevParams& p, int rank_lds, int dtype, char* out, int cap) {
+    if (dtype != OBS_F32 && dtype != OBS_F16 && dtype != OBS_BF16) return -1;
+    int k = -1;
+    select_obs(p, rank_lds, dtype, [&](auto, auto, const char* fmt, auto... targs) {
+        k = snprintf(out, (size_t)cap, fmt, targs...);
+    });
+    return k;
+}
+
+hipError_t launch_obs(const DevParams& p, int env_begin, int n, void* amap_, void* avec_, void* cmap_, void* cvec_,
+                      int wpb, size_t lds, hipStream_t s, int rank_lds, const uint8_t* mask, int dtype) {
+    if (dtype != OBS_F32 && dtype != OBS_F16 && dtype != OBS_BF16) return hipErrorInvalidValue;
+    const dim3 g(blocks_for(n, wpb)), b(256);
+    select_obs(p, rank_lds, dtype, [&](auto small, auto kernel, auto...) {
+        typedef typename obs_kernel_out<decltype(kernel)>::type OT;
+        OT *amap = (OT*)amap_, *avec = (OT*)avec_, *cmap = (OT*)cmap_, *cvec = (OT*)cvec_;
+        if constexpr (decltype(small)::value)
+            hipLaunchKernelGGL(kernel, g, b, (size_t)rank_lds + lds * wpb, s, p, env_begin, n, amap, avec, cmap, cvec,
+                               wpb, (int)lds, rank_lds, mask);
+        else
+            hipLaunchKernelGGL(kernel, g, b, lds * wpb, s, p, env_begin, n, amap, avec, cmap, cvec, wpb, (int)lds,
+                               mask);
     });
     return hipGetLastError();
 }

@@ -62,6 +62,10 @@ enum : int { OBS_F32 = 0, OBS_F16 = 1, OBS_BF16 = 2 };   // = MDL_OBS_* (mdl_eng
 hipError_t launch_obs(const DevParams& p, int env_begin, int n, void* amap, void* avec, void* cmap, void* cvec,
                       int wpb, size_t lds, hipStream_t s, int rank_lds = 0, const uint8_t* mask = nullptr,
                       int dtype = 0);
+// The symbol (as rocprof names it) of the builder launch_obs runs for these arguments, from the
+// selection launch_obs launches through (select_obs, mdl_kernels.hip).  Returns snprintf's count,
+// -1 for an unknown dtype.
+int obs_kernel_name(const DevParams& p, int rank_lds, int dtype, char* out, int cap);
 // A launch's own completion word (host-mapped): every wave of its grid counts itself in the
 // running device counter `ctr` (never reset: `base` is its value before the launch) after a
 // system-scope release of its stores; the last one writes `value` to `seq`.  seq == nullptr: none;

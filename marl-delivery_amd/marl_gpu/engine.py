@@ -431,6 +431,13 @@ class BatchedEnv:
               "mdl_step_kernel_name")
         return buf.value.decode()
 
+    def obs_kernel_name(self, dtype: torch.dtype = torch.float32) -> str:
+        """The kernel symbol (as rocprof names it) ``build_obs(dtype=dtype)`` launches -- from the
+        engine, whose builder launch goes through the same selection."""
+        buf = C.create_string_buffer(128)
+        check(lib().mdl_obs_kernel_name(self._h, _obs_dtype(dtype), buf, 128), "mdl_obs_kernel_name")
+        return buf.value.decode()
+
     def last_step_layout(self) -> str | None:
         """The layout of the last ``step`` launch (None before the first), as the engine recorded it."""
         lay = C.c_int32()

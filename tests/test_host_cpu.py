@@ -574,6 +574,40 @@ def test_launch_matrix_lists_every_launch_kernel(tmp_path):
         assert any(n.startswith(_launch_mangled_prefix(s)) for n in built), s
 
 
+# ---- tests/obs_matrix.py: the observation builders ----
+OBS_KERNELS = ("k_obs", "k_obs_h", "k_obs_small", "k_obs_small_h")
+
+
+@pytest.mark.skipif(not os.path.exists(f"{LLVM_BIN}/llvm-readelf"), reason="ROCm LLVM tools absent")
+def test_obs_matrix_lists_every_builder_kernel(tmp_path):
+    """The builder kernels in the library's gfx950 code objects are exactly the 18 symbols of
+    tests/obs_matrix.py (two k_obs, four k_obs_h, four k_obs_small, eight k_obs_small_h), each of which
+    test_gpu_obs_matrix.py runs against the oracle.  The filter takes the whole mangled name, so the fused
+    step kernels (k_step_obs, tests/step_matrix.py) are not among them."""
+    from collections import Counter
+
+    import obs_matrix
+    from marl_gpu import _lib
+    res = _kernel_resources(_lib.LIB_PATH, tmp_path)
+    pat = re.compile(r"^_ZN3mdl(?:%s)I" % "|".join(f"{len(k)}{k}" for k in OBS_KERNELS))
+    built = sorted(n for n in res if pat.match(n))
+    assert not any("k_step" in n for n in built) and any("k_step_obs" in n for n in res)
+    cxxfilt = f"{LLVM_BIN}/llvm-cxxfilt"
+    if os.path.exists(cxxfilt):
+        out = subprocess.run([cxxfilt] + built, capture_output=True, text=True, check=True).stdout.split("\n")
+        have = [re.sub(r"^void ", "", d.split("(")[0]) for d in out if d]
+    else:   # no demangler: match each symbol's mangled name + template arguments
+        by_prefix = {_mangled_prefix(s): s for s in obs_matrix.SYMBOLS}
+        have = [next((s for p, s in by_prefix.items() if n.startswith(p)), n) for n in built]
+    assert len(have) == len(set(have)) == len(built), Counter(have).most_common(3)
+    assert set(have) == set(obs_matrix.SYMBOLS), (sorted(set(have) - set(obs_matrix.SYMBOLS)),
+                                                  sorted(set(obs_matrix.SYMBOLS) - set(have)))
+    assert Counter(s.split("<")[0] for s in have) == {"mdl::k_obs": 2, "mdl::k_obs_h": 4, "mdl::k_obs_small": 4,
+                                                      "mdl::k_obs_small_h": 8}
+    for s in obs_matrix.SYMBOLS:   # the mangling rule the fallback uses holds for every symbol
+        assert any(n.startswith(_mangled_prefix(s)) for n in built), s
+
+
 def test_launch_matrix_shapes_select_their_symbols():
     """Each launch-matrix entry's shape selects its symbol by the dispatch rules (restated here: nch_for,
     launch_reset, launch_cycle_begin, launch_alt_obs, launch_alt_transition), fits its map and keeps to
