@@ -909,6 +909,20 @@ void or_greedy_init(OGreedy* g, const OEnv* e) {
     greedy_append(g, e);
 }
 
+/* The agent's own state, read only: returns n; list / free_ receive n entries (room for 2P + 1), */
+/* target / carrying A entries (robots_target and the inner robots' carrying). NULL skips one.   */
+int or_greedy_get(const OGreedy* g, int* list, uint8_t* free_, int* target, int* carrying) {
+    for (int j = 0; j < g->n; j++) {
+        if (list) list[j] = g->list[j];
+        if (free_) free_[j] = g->free_[j];
+    }
+    for (int i = 0; i < g->A; i++) {
+        if (target) target[i] = g->target[i];
+        if (carrying) carrying[i] = g->robots[i].carrying;
+    }
+    return g->n;
+}
+
 /* greedyagent.py:6-41 run_bfs(map, start, goal): returns the move, *dist = d after the move */
 static int greedy_bfs(OGreedy* g, const OEnv* e, int sr, int sc, int gr, int gc, int* dist) {
     const int H = e->H, W = e->W;

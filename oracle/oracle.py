@@ -80,6 +80,8 @@ def lib():
         L.or_greedy_free.argtypes = [vp]
         L.or_greedy_init.argtypes = [vp, vp]
         L.or_greedy_actions.argtypes = [vp, vp, vp, vp]
+        L.or_greedy_get.restype = i32
+        L.or_greedy_get.argtypes = [vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -285,7 +287,7 @@ class OracleGreedy:
     """``GreedyAgents`` (greedyagent.py) restated in C, bug for bug (see mdl_oracle.c)."""
 
     def __init__(self, env: OracleEnv):
-        self.A = env.A
+        self.A, self.P = env.A, env.P
         self.h = lib().or_greedy_new(env.A, env.P, env.H, env.W)
         lib().or_greedy_init(self.h, env.h)       # GreedyAgents(); init_agents(env.reset() state)
 
@@ -300,6 +302,16 @@ class OracleGreedy:
         op = np.zeros(self.A, np.uint8)
         lib().or_greedy_actions(self.h, env.h, _p(mv), _p(op))
         return mv, op
+
+    def record(self):
+        """The agent's own state: dict of n, list [n] (package ids in append order), free [n]
+        (packages_free), target [A] (robots_target, 0 = 'free') and carrying [A] (the inner robots')."""
+        lst = np.zeros(2 * self.P + 1, np.int32)
+        fr = np.zeros(2 * self.P + 1, np.uint8)
+        tg = np.zeros(self.A, np.int32)
+        ca = np.zeros(self.A, np.int32)
+        n = lib().or_greedy_get(self.h, _p(lst), _p(fr), _p(tg), _p(ca))
+        return dict(n=n, list=lst[:n].copy(), free=fr[:n].copy(), target=tg, carrying=ca)
 
 
 def idq_convert_state(grid, t, robots1, trk_rows, idx):
