@@ -518,6 +518,21 @@ int mdl_step_obs_as(MdlEngine* eng, const uint8_t* actions, int32_t action_forma
                     float* r_shaped, uint8_t* done, int32_t dtype, void* actor_map, void* actor_vec,
                     void* critic_map, void* critic_vec, void* stream);
 
+/* Robot-centred actor-map windows (no reference counterpart: a crop of convert_observation's tensor).
+ * For radius R = `radius` in [1, MDL_EGO_MAX_RADIUS] and K = 2R + 1, robot a on 0-based cell (r, c):
+ *   actor_ego [n][A][6][K][K],  ego[a][ch][i][j] = actor_map[a][ch][r - R + i][c - R + j]
+ * where that cell lies inside the env's map (actor_map: exactly what mdl_build_obs writes for the same
+ * state, tracker mode and clock); outside the map channel 0 (obstacles) is 1.0 -- an off-map cell cannot
+ * be entered -- and channels 1-5 are 0.0.  Channel 1 is therefore a single 1.0 at (R, R).  The carried
+ * package's target (channel 5) may lie outside the window, which is then all zero in that channel; the
+ * actor vector still carries the target.  `dtype` (MDL_OBS_*) is the element type, the half types the
+ * float32 values rounded once (values are 0 or 1).  The output shape does not depend on the map, so the
+ * range is checked against [0, E) only and may cross map shapes.  Asynchronous on `stream`, no host
+ * round trip.  A radius outside [1, MDL_EGO_MAX_RADIUS] or an unknown dtype fails with a message. */
+#define MDL_EGO_MAX_RADIUS 15
+int mdl_build_obs_ego(MdlEngine* eng, int32_t env_begin, int32_t n, int32_t radius, int32_t dtype, void* actor_ego,
+                      void* stream);
+
 /* State snapshot into caller DEVICE buffers (async on `stream`).  Any pointer may be NULL.
  *   robots   int32 [E][A][3]  (row, col, carrying), 0-indexed
  *   pkgs     int32 [E][P][8]  (sr, sc, tr, tc, start_time, deadline, id, status 0 None/1 waiting/2 in_transit/3 delivered)

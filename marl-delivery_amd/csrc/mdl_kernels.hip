@@ -1463,6 +1463,9 @@ __global__ __launch_bounds__(256) void k_obs_h(DevParams p, int env_begin, int n
     run(staged_tracker<STALE>(S, P));
 }
 
+// robot-centred actor-map windows (k_ego_maps), on the tracker staging above
+#include "mdl_ego.hpp"
+
 // ------------------------------------------------------ dict views (helpers)
 // record: [t, A, n_slots, map] + A*(r, c, carry) + n_slots*(id, status, sr, sc, tr, tc, st, dl)
 struct ViewLdsPre {
@@ -2472,6 +2475,40 @@ hipError_t launch_obs(const DevParams& p, int env_begin, int n, void* amap_, voi
         else
             hipLaunchKernelGGL(kernel, g, b, lds * wpb, s, p, env_begin, n, amap, avec, cmap, cvec, wpb, (int)lds,
                                mask);
+    });
+    return hipGetLastError();
+}
+
+// ---- the window builder (mdl_ego.hpp) ----
+// Robots per image for radius R: the whole env where its image fits EGO_IMAGE_BYTES and what the
+// fixed part of the slice leaves of `budget`; 0 if not even one robot's windows fit.
+int ego_group(int A, int P, int maxHW, int R, size_t budget) {
+    const int K = 2 * R + 1;
+    const size_t fixed = ego_fixed_bytes(P, maxHW);
+    if (fixed >= budget) return 0;
+    const size_t room = budget - fixed < (size_t)EGO_IMAGE_BYTES ? budget - fixed : (size_t)EGO_IMAGE_BYTES;
+    int G = A;
+    while (G > 0 && align16(sizeof(uint32_t) * (size_t)ego_image_words(G, K)) > room) G--;
+    return G;
+}
+size_t ego_lds(int P, int maxHW, int G, int R) { return ego_lds_bytes(P, maxHW, G, 2 * R + 1); }
+
+hipError_t launch_ego(const DevParams& p, int env_begin, int n, int R, int dtype, void* out, int wpb, size_t lds,
+                      int G, hipStream_t s) {
+    if (dtype != OBS_F32 && dtype != OBS_F16 && dtype != OBS_BF16) return hipErrorInvalidValue;
+    if (R < 1 || R > EGO_RMAX || G < 1 || wpb < 1) return hipErrorInvalidValue;
+    const dim3 g(blocks_for(n, wpb)), b(256);
+    with_int<0, 1>(p.stale != 0, [&](auto st) {
+        constexpr bool ST = decltype(st)::value != 0;
+        if (dtype == OBS_F32)
+            hipLaunchKernelGGL((k_ego_maps<ST, float>), g, b, lds * wpb, s, p, env_begin, n, R, (float*)out, wpb,
+                               (int)lds, G);
+        else if (dtype == OBS_F16)
+            hipLaunchKernelGGL((k_ego_maps<ST, f16_t>), g, b, lds * wpb, s, p, env_begin, n, R, (f16_t*)out, wpb,
+                               (int)lds, G);
+        else
+            hipLaunchKernelGGL((k_ego_maps<ST, bf16_t>), g, b, lds * wpb, s, p, env_begin, n, R, (bf16_t*)out, wpb,
+                               (int)lds, G);
     });
     return hipGetLastError();
 }

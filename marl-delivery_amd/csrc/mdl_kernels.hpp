@@ -66,6 +66,13 @@ hipError_t launch_obs(const DevParams& p, int env_begin, int n, void* amap, void
 // selection launch_obs launches through (select_obs, mdl_kernels.hip).  Returns snprintf's count,
 // -1 for an unknown dtype.
 int obs_kernel_name(const DevParams& p, int rank_lds, int dtype, char* out, int cap);
+// The window builder (k_ego_maps, mdl_ego.hpp): out [n][A][6][K][K] of `dtype`, K = 2R + 1, for envs
+// [env_begin, env_begin + n) of any map shapes.  ego_group: the robots whose windows share one LDS
+// image for radius R (0: the slice does not fit `budget`); ego_lds: the per-wave slice for that group.
+int ego_group(int A, int P, int maxHW, int R, size_t budget);
+size_t ego_lds(int P, int maxHW, int G, int R);
+hipError_t launch_ego(const DevParams& p, int env_begin, int n, int R, int dtype, void* out, int wpb, size_t lds,
+                      int G, hipStream_t s);
 // A launch's own completion word (host-mapped): every wave of its grid counts itself in the
 // running device counter `ctr` (never reset: `base` is its value before the launch) after a
 // system-scope release of its stores; the last one writes `value` to `seq`.  seq == nullptr: none;

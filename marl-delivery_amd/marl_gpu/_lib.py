@@ -36,6 +36,7 @@ MDL_OBS_BUILDER_GENERIC = 1
 MDL_OBS_F32 = 0
 MDL_OBS_F16 = 1
 MDL_OBS_BF16 = 2
+MDL_EGO_MAX_RADIUS = 15
 MDL_STEP_LAYOUT_AUTO = 0
 MDL_STEP_LAYOUT_WAVE = 1
 MDL_STEP_LAYOUT_ROWS = 2
@@ -88,6 +89,7 @@ SIGNATURES = {
     "mdl_step_floor": (C.c_int, [_vp, _i32, _vp]),
     "mdl_build_obs": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "mdl_build_obs_as": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "mdl_build_obs_ego": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "mdl_build_obs_alt": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp]),
     "mdl_alt_pre_bytes": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
     "mdl_alt_transition": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),

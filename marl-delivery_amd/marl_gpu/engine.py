@@ -551,6 +551,57 @@ class BatchedEnv:
             check(lib().mdl_build_obs_as(self._h, env_begin, n, dt, *op, self._stream()), "mdl_build_obs_as")
         return out
 
+    # ---- robot-centred actor-map windows ----
+    @staticmethod
+    def _ego_radius(radius):
+        if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) \
+                or not 1 <= int(radius) <= _lib.MDL_EGO_MAX_RADIUS:
+            raise ValueError(f"radius must be an int in [1, {_lib.MDL_EGO_MAX_RADIUS}], not {radius!r}")
+        return int(radius)
+
+    def ego_buffers(self, radius: int, n=None, dtype: torch.dtype = torch.float32):
+        """A new tensor [n, A, 6, K, K] (K = 2 * radius + 1) of ``dtype`` for ``build_obs_ego``."""
+        _obs_dtype(dtype)
+        K = 2 * self._ego_radius(radius) + 1
+        n = self.E if n is None else int(n)
+        return torch.empty((n, self.A, 6, K, K), dtype=dtype, device=self.device)
+
+    def build_obs_ego(self, radius: int, env_begin: int = 0, n: int | None = None, out: torch.Tensor | None = None,
+                      dtype: torch.dtype = torch.float32):
+        """Each robot's ``K x K`` window of its actor map, centred on the robot (K = 2 * radius + 1,
+        radius in 1..15), for envs [env_begin, env_begin + n): a tensor [n, A, 6, K, K].
+
+        ``ego[e, a, ch, i, j] = build_obs()["actor_map"][e, a, ch, r - radius + i, c - radius + j]`` for
+        robot a on cell (r, c) where that cell lies inside the map -- same tracker mode, stale survivors
+        and clock.  Outside the map channel 0 (obstacles) is 1.0 (an off-map cell cannot be entered) and
+        channels 1-5 are 0.0, so channel 1 is a single 1.0 at (radius, radius) and the reference's actor
+        constructs unchanged with ``obs_shape = (6, K, K)``.  The carried package's target (channel 5)
+        may fall outside the window -- that is what a window means; channel 5 is then all zero while
+        the robot carries, and the actor vector still holds the target.
+
+        The shape does not depend on the map, so the range may cross map shapes (``build_obs`` refuses
+        that).  ``dtype`` as ``build_obs``: the half types hold 0 / 1.0 exactly.  ``out``: a contiguous
+        tensor of ``dtype`` on the engine's device with n * A * 6 * K * K entries."""
+        dt = _obs_dtype(dtype)
+        R = self._ego_radius(radius)
+        K = 2 * R + 1
+        env_begin = int(env_begin)
+        n = self.E - env_begin if n is None else int(n)
+        if env_begin < 0 or n < 0 or env_begin + n > self.E:
+            raise IndexError(f"env range [{env_begin}, {env_begin + n}) outside [0, {self.E})")
+        need = n * self.A * 6 * K * K
+        if out is None:
+            out = self.ego_buffers(R, n, dtype)
+        else:
+            name = str(dtype).replace("torch.", "")
+            self._check_buf(out, dtype, need, (TypeError, f"out must be a {name} tensor"),
+                            (ValueError, f"out must be contiguous on {self.device}"),
+                            (ValueError, f"out holds {{n}} entries, needs {need} ({n}, {self.A}, 6, {K}, {K})"))
+        if n == 0:
+            return out
+        check(lib().mdl_build_obs_ego(self._h, env_begin, n, R, dt, ptr(out), self._stream()), "mdl_build_obs_ego")
+        return out
+
     # ---- IDQ / qmix featurizers (SURVEY.md §8(f)2) ----
     def build_obs_alt(self, env_begin: int = 0, n: int | None = None, out: dict | None = None,
                       state_shape=None, which=("idq_obs", "qmix_state")):

@@ -62,11 +62,19 @@ class MappoRollout(Graphed):
     nearest-even (``BatchedEnv.build_obs(dtype=)``), half the bytes, and actor and critic receive
     tensors of that type (a policy under autocast, or one that casts its inputs).  Rewards, values,
     log-probs, advantages and returns stay float32.
+
+    ego_radius: None (the default: nothing changes), or a radius R in 1..15 -- the actor then sees each
+    robot's ``K x K`` window of its map, centred on the robot (K = 2R + 1, ``BatchedEnv.build_obs_ego``):
+    ``mb_obs`` and ``next_obs["actor_map"]`` are [.., A, 6, K, K] in ``obs_dtype``, the actor receives
+    obs [E*A, 6, K, K], and every step is ``step_obs`` of the other three tensors followed by
+    ``build_obs_ego`` into the next slot (the first observation likewise).  The critic keeps the full
+    map, so the envs must still share one map shape.
     """
 
     def __init__(self, env, rollout_steps: int, seed: int = 0, gamma: float = 0.99, gae_lambda: float = 0.95,
-                 avail: bool = False, obs_dtype: torch.dtype = torch.float32):
+                 avail: bool = False, obs_dtype: torch.dtype = torch.float32, ego_radius: int | None = None):
         self.env = env
+        self.ego_radius = None if ego_radius is None else env._ego_radius(ego_radius)
         if obs_dtype not in (torch.float32, torch.float16, torch.bfloat16):
             raise TypeError(f"obs_dtype must be torch.float32, torch.float16 or torch.bfloat16, not {obs_dtype}")
         self.obs_dtype = obs_dtype
@@ -80,7 +88,11 @@ class MappoRollout(Graphed):
         f = dict(dtype=torch.float32, device=dev)
         T = self.T
         o = dict(dtype=obs_dtype, device=dev)
-        self.mb_obs = torch.zeros((T, E, A, 6, H, W), **o)
+        if self.ego_radius is None:
+            self.mb_obs = torch.zeros((T, E, A, 6, H, W), **o)
+        else:
+            K = 2 * self.ego_radius + 1
+            self.mb_obs = torch.zeros((T, E, A, 6, K, K), **o)
         self.mb_vector_obs = torch.zeros((T, E, A, env.actor_vec_dim), **o)
         self.mb_global_states = torch.zeros((T, E, 4, H, W), **o)
         self.mb_global_vector = torch.zeros((T, E, env.critic_vec_dim), **o)
@@ -90,6 +102,8 @@ class MappoRollout(Graphed):
         self.mb_dones = torch.zeros((T, E), dtype=torch.uint8, device=dev)
         self.mb_values = torch.zeros((T, E), **f)
         self.next_obs = env.obs_buffers(E, H, W, obs_dtype)
+        if self.ego_radius is not None:
+            self.next_obs["actor_map"] = env.ego_buffers(self.ego_radius, E, obs_dtype)
         self._r_env = torch.zeros(E, dtype=torch.float64, device=dev)
         self._graph_out = None
         self.mb_avail = torch.ones((T, E, A, ACTION_DIM), dtype=torch.uint8, device=dev) if avail else None
@@ -122,7 +136,13 @@ class MappoRollout(Graphed):
     def _run(self, actor, critic, dev_offset: bool):
         env, T = self.env, self.T
         E, A = env.E, env.A
-        env.build_obs(out=self._slot(0), dtype=self.obs_dtype)   # current obs = f(current state, tracker)
+        R = self.ego_radius
+        # with a radius the actor map is the window builder's
+        which = ("actor_vec", "critic_map", "critic_vec") if R is not None else \
+            ("actor_map", "actor_vec", "critic_map", "critic_vec")
+        env.build_obs(out=self._slot(0), which=which, dtype=self.obs_dtype)   # current obs = f(current state, tracker)
+        if R is not None:
+            env.build_obs_ego(R, out=self.mb_obs[0], dtype=self.obs_dtype)
         for step in range(T):
             obs = self.mb_obs[step]
             logits = actor(obs.reshape(E * A, *obs.shape[2:]), self.mb_vector_obs[step].reshape(E * A, -1))
@@ -135,16 +155,18 @@ class MappoRollout(Graphed):
             self.offset += 1
             self.mb_values[step] = critic(self.mb_global_states[step], self.mb_global_vector[step]).reshape(E)
             # step + the next observations in one launch (MAPPO/trainer.py:229-286)
+            nxt = self._slot(step + 1) if step + 1 < T else self.next_obs
             env.step_obs(self.mb_actions[step], auto_reset=True,
                          out=(self._r_env, self.mb_rewards[step], self.mb_dones[step]),
-                         obs_out=self._slot(step + 1) if step + 1 < T else self.next_obs,
-                         obs_dtype=self.obs_dtype)
+                         obs_out=nxt, which=which, obs_dtype=self.obs_dtype)
+            if R is not None:
+                env.build_obs_ego(R, out=nxt["actor_map"], dtype=self.obs_dtype)
         if dev_offset:
             check(lib().mdl_counter_add(ptr(self._off_dev), T, stream_handle(env.device)), "mdl_counter_add")
         next_value = critic(self.next_obs["critic_map"], self.next_obs["critic_vec"]).reshape(E)
         adv, ret = gae(self.mb_rewards, self.mb_values, next_value, self.mb_dones, self.gamma, self.gae_lambda)
-        H, W = obs.shape[-2:]
-        return (self.mb_obs.reshape(-1, 6, H, W), self.mb_vector_obs.reshape(T * E * A, -1),
+        H, W = self.mb_global_states.shape[-2:]
+        return (self.mb_obs.reshape(-1, *self.mb_obs.shape[3:]), self.mb_vector_obs.reshape(T * E * A, -1),
                 self.mb_global_states.reshape(T * E, 4, H, W), self.mb_global_vector.reshape(T * E, -1),
                 self.mb_actions.reshape(-1).long(), self.mb_log_probs.reshape(-1),
                 adv.reshape(T * E, 1).repeat(1, A).reshape(-1), ret.reshape(-1), self.mb_rewards)

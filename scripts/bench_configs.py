@@ -10,6 +10,8 @@
   --config rollout / rollout_graph   MAPPO rollout on the device
   --obs-dtype       float16 / bfloat16 observations: configs 3 / 3b time step_obs and build_obs for float32
                     and the half types in one process; rollout / rollout_graph collect in that type
+  --ego-radius      R (or several): configs 3 / 5 time build_obs_ego (float32 and bfloat16, all envs in one
+                    call) beside the full actor maps' build_obs in one process
   --config alt      IDQ/qmix featurizers (§8(f)2)
   --config greedy   batched greedy baseline (§8(f)3)
   --qmix            QMIX episode collection: the masked step against the full step, and one collector
@@ -229,6 +231,67 @@ def run_obs_dtype(cfg, steps, warmup, names, rounds=3):
                       build_obs_roofline_frac=b / (best * 1e-6) / 1e9 / HBM)
     print(json.dumps({"config": cfg + ":obs_dtype", "envs": E, "agents": A, "packages": P, "rounds": rounds,
                       "replays": reps, "calls_per_graph": C, "dtypes": res}), flush=True)
+    env.close()
+
+
+def run_ego(cfg, radii, steps, warmup, rounds=3):
+    """Robot-centred actor-map windows ("Egocentric actor windows"), config 3 or 5: in one
+    process, on one engine, ``build_obs_ego`` over all of the rank's envs in one call, float32 and
+    bfloat16 at each radius, beside the existing full-map ``build_obs(which=("actor_map",))`` (float32;
+    config 5: per chunk of 4,096 envs, as its usual leg builds them).  Every figure is a hipGraph of 10
+    captured calls, each graph captured once and replayed in turn, ``rounds`` times."""
+    import marl_gpu
+    from marl_gpu.maps import grid_array, load_map, map_path
+    dev = torch.device("cuda", 0)
+    if cfg == "3":
+        E, A, P, T, H = 16384, 5, 50, 500, 10
+        env = marl_gpu.BatchedEnv(grid_array(load_map(map_path("map1.txt"))), E, A, P, T, seed=42, tracker="mappo",
+                                  max_other_robots=4, max_packages_obs=5)
+        chunk = E
+    elif cfg == "5":
+        E, A, P, T, H = 131072 // 8, 16, 100, 500, 64
+        env = marl_gpu.BatchedEnv(grid_array(load_map(map_path("synthetic64.txt"))), E, A, P, T, seed=7,
+                                  tracker="mappo", max_other_robots=15, max_packages_obs=20, max_robots_state=16,
+                                  max_packages_state=100)
+        chunk = int(os.environ.get("MDL_OBS_CHUNK", "4096"))
+    else:
+        raise SystemExit("--ego-radius goes with --config 3 or --config 5")
+    env.reset()
+    gen = torch.Generator(device=dev).manual_seed(0)
+    G, C = 50, 10
+    acts = torch.randint(0, 15, (G, E, A), generator=gen, device=dev, dtype=torch.int32).to(torch.uint8)
+    for k in range(warmup):
+        env.step(acts[k % G])
+    nchunks = E // chunk
+    full = {"actor_map": torch.empty((chunk, A, 6, H, H), dtype=torch.float32, device=dev)}
+
+    def full_():
+        for k in range(C):
+            env.build_obs((k % nchunks) * chunk, chunk, out=full, which=("actor_map",))
+
+    graphs = {"full_map_float32": (_graph_of(full_), full, chunk * A * 6 * H * H * 4)}
+    for R in radii:
+        for n in ("float32", "bfloat16"):
+            buf = env.ego_buffers(R, dtype=OBS_DTYPES[n])
+
+            def ego_(buf=buf, R=R, n=n):
+                for k in range(C):
+                    env.build_obs_ego(R, out=buf, dtype=OBS_DTYPES[n])
+
+            graphs[f"ego_r{R}_{n}"] = (_graph_of(ego_), buf, buf.numel() * buf.element_size())
+    reps = max(1, steps // 50)
+    t = {k: [] for k in graphs}
+    for _ in range(rounds):
+        for k, (g, _, _) in graphs.items():
+            t[k].append(_replay_us(g, reps, C))
+    res = {}
+    for k, (_, _, b) in graphs.items():
+        best = min(t[k])
+        res[k] = {"us_per_call": t[k], "envs_per_call": chunk if k.startswith("full") else E, "bytes_written": b,
+                  "achieved_GBs": b / (best * 1e-6) / 1e9, "frac_of_8TBs": b / (best * 1e-6) / 1e9 / HBM}
+    res["full_map_float32"]["us_all_envs"] = [x * nchunks for x in t["full_map_float32"]]
+    print(json.dumps({"config": cfg + ":ego", "envs": E, "agents": A, "packages": P, "map": [H, H], "radii": list(radii),
+                      "rounds": rounds, "replays": reps, "calls_per_graph": C, "builds": res}), flush=True)
     env.close()
 
 
@@ -1085,7 +1148,14 @@ def main():
                     help="float32, float16 or bfloat16 (or several, comma-separated): with a half type, configs 3 / 3b "
                          "print the float32-against-half comparison of one process instead of their usual line, and "
                          "rollout / rollout_graph collect into buffers of that type")
+    ap.add_argument("--ego-radius", default="",
+                    help="a radius in 1..15 (or several, comma-separated): configs 3 / 5 print the window builder's "
+                         "times (build_obs_ego, float32 and bfloat16) beside the full actor maps' instead of their "
+                         "usual line")
     a = ap.parse_args()
+    radii = [int(x) for x in a.ego_radius.split(",") if x]
+    if any(not 1 <= r <= 15 for r in radii):
+        ap.error(f"--ego-radius: {a.ego_radius!r} (1..15)")
     obs_dtypes = a.obs_dtype.split(",")
     if any(n not in OBS_DTYPES for n in obs_dtypes):
         ap.error(f"--obs-dtype: {a.obs_dtype!r} (float32, float16, bfloat16)")
@@ -1116,6 +1186,8 @@ def main():
             run_alt(a.steps)
         elif c == "greedy":
             run_greedy(a.steps)
+        elif radii:
+            run_ego(c, radii, a.steps, a.warmup)
         elif c in ("3", "3b") and half:
             run_obs_dtype(c, a.steps, a.warmup, half)
         else:
