@@ -533,6 +533,17 @@ int mdl_step_obs_as(MdlEngine* eng, const uint8_t* actions, int32_t action_forma
 int mdl_build_obs_ego(MdlEngine* eng, int32_t env_begin, int32_t n, int32_t radius, int32_t dtype, void* actor_ego,
                       void* stream);
 
+/* mdl_build_obs_ego under a row mask, for the episode loops (after mdl_step_episode, with its `filled`).
+ * rows: DEVICE uint8 [E], indexed by ENV ID (rows[e] for env e of [env_begin, env_begin + n), not by the
+ * output row e - env_begin); non-zero = build.  The output row of env e is the unmasked call's
+ * (actor_ego + (e - env_begin) * A * 6 * K * K elements); rows of unmarked envs are not written, not one
+ * byte -- they keep what the caller's buffer held.  The mask is read on the device by the launch itself:
+ * the call is asynchronous on `stream` with no host round trip, so it can be captured in a hipGraph.
+ * Every other check and meaning is mdl_build_obs_ego's.  rows == NULL fails with a message: the unmasked
+ * entry point exists for that case. */
+int mdl_build_obs_ego_masked(MdlEngine* eng, int32_t env_begin, int32_t n, const uint8_t* rows, int32_t radius,
+                             int32_t dtype, void* actor_ego, void* stream);
+
 /* State snapshot into caller DEVICE buffers (async on `stream`).  Any pointer may be NULL.
  *   robots   int32 [E][A][3]  (row, col, carrying), 0-indexed
  *   pkgs     int32 [E][P][8]  (sr, sc, tr, tc, start_time, deadline, id, status 0 None/1 waiting/2 in_transit/3 delivered)

@@ -199,7 +199,8 @@ __device__ __forceinline__ void ego_emit(const uint32_t* FB, int n, OT* dst) {
 }
 
 // out [n][A][6][K][K] of envs [env_begin, env_begin + n), K = 2R + 1; G robots per image (the host's
-// ego_group: the whole env where its image fits the slice).
+// ego_group: the whole env where its image fits the slice).  k_masked_ego_maps below repeats this body
+// behind a row mask: a change to one belongs in the other.
 template <bool STALE, class OT>
 __global__ __launch_bounds__(256) void k_ego_maps(DevParams p, int env_begin, int n, int R, OT* __restrict__ out,
                                                   int wpb, int lds_stride, int G) {
@@ -209,6 +210,42 @@ __global__ __launch_bounds__(256) void k_ego_maps(DevParams p, int env_begin, in
     const int w = xcd_block() * wpb + wave;
     if (wave >= wpb || w >= n) return;
     const int e = env_begin + w;
+    const int A = p.A, P = p.P;
+    unsigned char* base = smem + (size_t)wave * lds_stride;
+    ObsLdsPre S = obs_pre_carve(base, P);
+    const MapDesc md = p.maps[p.env_map ? p.env_map[e] : 0];
+    const int H = md.H, W = md.W, NW = (H * W + 31) >> 5;
+    const EgoLds L = ego_carve(base + obs_pre_bytes(P), NW);
+    const int t = p.es[e].t;
+    const uint32_t rv = lane < A ? p.rob[(size_t)e * A + lane] : 0u;
+    stage_tracker<STALE>(p, e, P, lane, S);
+    ego_prepare(staged_tracker<STALE>(S, P), L, p.gridbits + md.bits_off, NW, W, A, P, t, rob_cell(rv), rob_carry(rv));
+    const int per = 6 * (2 * R + 1) * (2 * R + 1);   // elements per robot
+    OT* dst = out + (size_t)w * A * per;
+    for (int a0 = 0; a0 < A; a0 += G) {   // uniform
+        const int na = min(G, A - a0);
+        ego_build_image(L, NW, H, W, R, a0, na);
+        [[clang::always_inline]] ego_emit(L.img, na * per, dst + (size_t)a0 * per);
+        wave_sync();   // the image is rebuilt for the next group
+    }
+}
+
+// k_ego_maps under a row mask (mdl_build_obs_ego_masked), on the same device functions: rows (uint8 [E],
+// indexed by env id, non-zero = build) marks the envs to build.  The wave of an unmarked env leaves after
+// one byte load, before it touches LDS, and writes nothing; the kernel has no workgroup barrier, so a
+// whole wave may return.  Launch shape, slices and output rows (env e = env_begin + w at
+// out + w * A * 6 * K * K) are k_ego_maps's.  A sibling, not a template flag: k_ego_maps keeps its code.
+template <bool STALE, class OT>
+__global__ __launch_bounds__(256) void k_masked_ego_maps(DevParams p, int env_begin, int n, int R,
+                                                         OT* __restrict__ out, int wpb, int lds_stride, int G,
+                                                         const uint8_t* __restrict__ rows) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int wave = wave_id();
+    const int lane = lane_id();
+    const int w = xcd_block() * wpb + wave;
+    if (wave >= wpb || w >= n) return;
+    const int e = env_begin + w;
+    if (__builtin_amdgcn_readfirstlane((int)rows[e]) == 0) return;   // wave-uniform: one byte, before any LDS use
     const int A = p.A, P = p.P;
     unsigned char* base = smem + (size_t)wave * lds_stride;
     ObsLdsPre S = obs_pre_carve(base, P);

@@ -1107,25 +1107,36 @@ int mdl_build_obs_as(MdlEngine* eng, int32_t env_begin, int32_t n, int32_t dtype
                         stream);
 }
 
-int mdl_build_obs_ego(MdlEngine* eng, int32_t env_begin, int32_t n, int32_t radius, int32_t dtype, void* actor_ego,
-                      void* stream) {
-    if (!eng) return fail("mdl_build_obs_ego: null engine");
-    if (!obs_dtype_ok(dtype))
-        return fail("mdl_build_obs_ego: unknown observation dtype %d (MDL_OBS_F32 / F16 / BF16)", dtype);
+// mdl_build_obs_ego and its masked form: rows null = every env of the range
+static int build_obs_ego(const char* who, MdlEngine* eng, int32_t env_begin, int32_t n, const uint8_t* rows,
+                         int32_t radius, int32_t dtype, void* actor_ego, void* stream) {
+    if (!eng) return fail("%s: null engine", who);
+    if (!obs_dtype_ok(dtype)) return fail("%s: unknown observation dtype %d (MDL_OBS_F32 / F16 / BF16)", who, dtype);
     if (radius < 1 || radius > MDL_EGO_MAX_RADIUS)
-        return fail("mdl_build_obs_ego: radius %d outside [1, %d]", radius, MDL_EGO_MAX_RADIUS);
+        return fail("%s: radius %d outside [1, %d]", who, radius, MDL_EGO_MAX_RADIUS);
     // any envs of [0, E): the windows have one shape whatever the maps, each wave reads its own env's
-    if (env_begin < 0 || n < 0 || env_begin + n > eng->p.E) return fail("mdl_build_obs_ego: env range out of bounds");
+    if (env_begin < 0 || n < 0 || env_begin + n > eng->p.E) return fail("%s: env range out of bounds", who);
     if (n == 0) return 0;
-    if (!actor_ego) return fail("mdl_build_obs_ego: null output");
+    if (!actor_ego) return fail("%s: null output", who);
     // the launch shape, as launch_obs's: waves per workgroup from the per-wave LDS slice
     const int G = mdl::ego_group(eng->p.A, eng->p.P, eng->maxHW, radius, LDS_BUDGET);
-    if (G < 1) return fail("mdl_build_obs_ego: the windows need more than %zu bytes of LDS per env", LDS_BUDGET);
+    if (G < 1) return fail("%s: the windows need more than %zu bytes of LDS per env", who, LDS_BUDGET);
     const size_t lds = mdl::ego_lds(eng->p.P, eng->maxHW, G, radius);
     DeviceGuard dg(eng->device);
-    HIPCHK(mdl::launch_ego(eng->p, env_begin, n, radius, dtype, actor_ego, waves_per_block(lds), lds, G,
+    HIPCHK(mdl::launch_ego(eng->p, env_begin, n, rows, radius, dtype, actor_ego, waves_per_block(lds), lds, G,
                            (hipStream_t)stream));
     return 0;
+}
+
+int mdl_build_obs_ego(MdlEngine* eng, int32_t env_begin, int32_t n, int32_t radius, int32_t dtype, void* actor_ego,
+                      void* stream) {
+    return build_obs_ego("mdl_build_obs_ego", eng, env_begin, n, nullptr, radius, dtype, actor_ego, stream);
+}
+
+int mdl_build_obs_ego_masked(MdlEngine* eng, int32_t env_begin, int32_t n, const uint8_t* rows, int32_t radius,
+                             int32_t dtype, void* actor_ego, void* stream) {
+    if (!rows) return fail("mdl_build_obs_ego_masked: null rows mask (mdl_build_obs_ego builds every env)");
+    return build_obs_ego("mdl_build_obs_ego_masked", eng, env_begin, n, rows, radius, dtype, actor_ego, stream);
 }
 
 int mdl_read_state(MdlEngine* eng, int32_t* robots, int32_t* pkgs, int32_t* t, double* total_reward,

@@ -2493,22 +2493,27 @@ int ego_group(int A, int P, int maxHW, int R, size_t budget) {
 }
 size_t ego_lds(int P, int maxHW, int G, int R) { return ego_lds_bytes(P, maxHW, G, 2 * R + 1); }
 
-hipError_t launch_ego(const DevParams& p, int env_begin, int n, int R, int dtype, void* out, int wpb, size_t lds,
-                      int G, hipStream_t s) {
+hipError_t launch_ego(const DevParams& p, int env_begin, int n, const uint8_t* rows, int R, int dtype, void* out,
+                      int wpb, size_t lds, int G, hipStream_t s) {
     if (dtype != OBS_F32 && dtype != OBS_F16 && dtype != OBS_BF16) return hipErrorInvalidValue;
     if (R < 1 || R > EGO_RMAX || G < 1 || wpb < 1) return hipErrorInvalidValue;
     const dim3 g(blocks_for(n, wpb)), b(256);
-    with_int<0, 1>(p.stale != 0, [&](auto st) {
+    auto go = [&](auto st, auto ot) {   // the tracker mode and element type chosen, the mask's form here
         constexpr bool ST = decltype(st)::value != 0;
-        if (dtype == OBS_F32)
-            hipLaunchKernelGGL((k_ego_maps<ST, float>), g, b, lds * wpb, s, p, env_begin, n, R, (float*)out, wpb,
-                               (int)lds, G);
-        else if (dtype == OBS_F16)
-            hipLaunchKernelGGL((k_ego_maps<ST, f16_t>), g, b, lds * wpb, s, p, env_begin, n, R, (f16_t*)out, wpb,
-                               (int)lds, G);
-        else
-            hipLaunchKernelGGL((k_ego_maps<ST, bf16_t>), g, b, lds * wpb, s, p, env_begin, n, R, (bf16_t*)out, wpb,
-                               (int)lds, G);
+        using OT = decltype(ot);
+        with_int<0, 1>(rows != nullptr, [&](auto mk) {
+            if constexpr (decltype(mk)::value != 0)
+                hipLaunchKernelGGL((k_masked_ego_maps<ST, OT>), g, b, lds * wpb, s, p, env_begin, n, R, (OT*)out, wpb,
+                                   (int)lds, G, rows);
+            else
+                hipLaunchKernelGGL((k_ego_maps<ST, OT>), g, b, lds * wpb, s, p, env_begin, n, R, (OT*)out, wpb,
+                                   (int)lds, G);
+        });
+    };
+    with_int<0, 1>(p.stale != 0, [&](auto st) {
+        if (dtype == OBS_F32) go(st, float{});
+        else if (dtype == OBS_F16) go(st, f16_t{});
+        else go(st, bf16_t{});
     });
     return hipGetLastError();
 }

@@ -71,8 +71,10 @@ int obs_kernel_name(const DevParams& p, int rank_lds, int dtype, char* out, int 
 // image for radius R (0: the slice does not fit `budget`); ego_lds: the per-wave slice for that group.
 int ego_group(int A, int P, int maxHW, int R, size_t budget);
 size_t ego_lds(int P, int maxHW, int G, int R);
-hipError_t launch_ego(const DevParams& p, int env_begin, int n, int R, int dtype, void* out, int wpb, size_t lds,
-                      int G, hipStream_t s);
+// rows (device uint8 [E], indexed by env id; may be null): env e is built only where rows[e] != 0, the
+// rows of the other envs stay unwritten (k_masked_ego_maps); null: every env of the range (k_ego_maps).
+hipError_t launch_ego(const DevParams& p, int env_begin, int n, const uint8_t* rows, int R, int dtype, void* out,
+                      int wpb, size_t lds, int G, hipStream_t s);
 // A launch's own completion word (host-mapped): every wave of its grid counts itself in the
 // running device counter `ctr` (never reset: `base` is its value before the launch) after a
 // system-scope release of its stores; the last one writes `value` to `seq`.  seq == nullptr: none;

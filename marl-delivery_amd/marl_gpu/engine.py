@@ -536,8 +536,9 @@ class BatchedEnv:
         ``dtype``: the tensors' element type.  torch.float16 / torch.bfloat16 tensors hold the float32
         values rounded once to nearest-even -- bit for bit ``build_obs()[k].to(dtype)`` -- written as
         half elements by the builder itself (half the bytes: for a policy under autocast, or smaller
-        rollout buffers).  ``out`` tensors must have that dtype.  (``step_episode``, the evaluator, the
-        QMIX collectors and the IDQ / qmix featurizers stay float32.)"""
+        rollout buffers).  ``out`` tensors must have that dtype.  (``step_episode``, the evaluator's and
+        the QMIX collectors' full-map paths and the IDQ / qmix featurizers stay float32; their window forms
+        take ``ego_dtype`` for the windows alone.)"""
         dt = _obs_dtype(dtype)
         n, g = self._obs_range(env_begin, n)
         H, W = g.shape
@@ -581,7 +582,22 @@ class BatchedEnv:
 
         The shape does not depend on the map, so the range may cross map shapes (``build_obs`` refuses
         that).  ``dtype`` as ``build_obs``: the half types hold 0 / 1.0 exactly.  ``out``: a contiguous
-        tensor of ``dtype`` on the engine's device with n * A * 6 * K * K entries."""
+        tensor of ``dtype`` on the engine's device with n * A * 6 * K * K entries.
+        ``build_obs_ego_masked`` is the form under a device mask of envs."""
+        return self._build_obs_ego(radius, env_begin, n, out, dtype, None)
+
+    def build_obs_ego_masked(self, radius: int, rows: torch.Tensor, env_begin: int = 0, n: int | None = None,
+                             out: torch.Tensor | None = None, dtype: torch.dtype = torch.float32):
+        """``build_obs_ego`` for the envs of [env_begin, env_begin + n) that ``rows`` marks, for the
+        episode loops (``rows`` = ``step_episode``'s ``filled``).  ``rows``: uint8 [E] on the engine's
+        device, indexed by env id whatever the range; a non-zero byte = build.  The launch reads the
+        mask itself (no host round trip, so the call can be captured in a hipGraph).  The output row of
+        an env is where ``build_obs_ego`` puts it; the rows of unmarked envs are not written -- in a
+        caller's ``out`` they keep what they held, and a fresh tensor (``out=None``) starts as zeros."""
+        self._check_mask(rows, "rows")
+        return self._build_obs_ego(radius, env_begin, n, out, dtype, rows)
+
+    def _build_obs_ego(self, radius, env_begin, n, out, dtype, rows):
         dt = _obs_dtype(dtype)
         R = self._ego_radius(radius)
         K = 2 * R + 1
@@ -591,7 +607,8 @@ class BatchedEnv:
             raise IndexError(f"env range [{env_begin}, {env_begin + n}) outside [0, {self.E})")
         need = n * self.A * 6 * K * K
         if out is None:
-            out = self.ego_buffers(R, n, dtype)
+            out = self.ego_buffers(R, n, dtype) if rows is None else \
+                torch.zeros((n, self.A, 6, K, K), dtype=dtype, device=self.device)
         else:
             name = str(dtype).replace("torch.", "")
             self._check_buf(out, dtype, need, (TypeError, f"out must be a {name} tensor"),
@@ -599,7 +616,11 @@ class BatchedEnv:
                             (ValueError, f"out holds {{n}} entries, needs {need} ({n}, {self.A}, 6, {K}, {K})"))
         if n == 0:
             return out
-        check(lib().mdl_build_obs_ego(self._h, env_begin, n, R, dt, ptr(out), self._stream()), "mdl_build_obs_ego")
+        if rows is None:
+            check(lib().mdl_build_obs_ego(self._h, env_begin, n, R, dt, ptr(out), self._stream()), "mdl_build_obs_ego")
+        else:
+            check(lib().mdl_build_obs_ego_masked(self._h, env_begin, n, ptr(rows), R, dt, ptr(out), self._stream()),
+                  "mdl_build_obs_ego_masked")
         return out
 
     # ---- IDQ / qmix featurizers ----

@@ -83,15 +83,26 @@ class Evaluator(Graphed):
                                   [E*A, n_actions]`` (``ActorNetwork.forward``, MAPPO/networks.py:52, as
                                   agent.py:86-104 calls it), actions as trainer ints.
     The policy's forward also runs on the finished envs' stale rows (as ``QmixCollector``'s agent
-    does); their actions are never used, the engine does not step them."""
+    does); their actions are never used, the engine does not step them.
 
-    def __init__(self, env, seed: int = 0):
+    ego_radius=R (1..15, K = 2R + 1; policies only, the greedy and tape kinds ignore it): the policy
+    is called as ``policy(actor_ego [E*A, 6, K, K], actor_vec [E*A, Dv])`` with each robot's window of
+    its actor map (``BatchedEnv.build_obs_ego``) in ``ego_dtype`` (torch.float32, float16 or bfloat16;
+    actor_vec stays float32).  Each step is then ``step_episode`` for the vectors and
+    ``build_obs_ego_masked`` over the envs it stepped."""
+
+    def __init__(self, env, seed: int = 0, ego_radius: int | None = None, ego_dtype: torch.dtype = torch.float32):
         self._hw = env.single_map_shape("Evaluator")
+        self.ego_radius = None if ego_radius is None else env._ego_radius(ego_radius)
+        self.ego_dtype = ego_dtype
+        if self.ego_radius is not None:
+            env.ego_buffers(self.ego_radius, 0, ego_dtype)   # raises on a dtype the builder does not write
         self.env = env
         self.seed = int(seed)
         self._init_graphs(env.device)
         E, A, dev = env.E, env.A, env.device
         self.active = torch.zeros(E, dtype=torch.uint8, device=dev)
+        self.filled = torch.zeros(E, dtype=torch.uint8, device=dev)   # the envs the last step moved (windows)
         self.actions = torch.zeros((E, A), dtype=torch.uint8, device=dev)
         self.rewards = torch.zeros(E, dtype=torch.float64, device=dev)
         self.delivered = torch.zeros(E, dtype=torch.int32, device=dev)
@@ -195,12 +206,18 @@ class Evaluator(Graphed):
         if kind == "greedy":
             env.greedy_init()
         elif kind == "policy":
+            R = self.ego_radius
             if self._obs is None:
                 H, W = self._hw
                 f = dict(dtype=torch.float32, device=env.device)
-                self._obs = dict(actor_map=torch.empty((env.E, env.A, 6, H, W), **f),
-                                 actor_vec=torch.empty((env.E, env.A, env.actor_vec_dim), **f))
-            env.build_obs(out=self._obs, which=("actor_map", "actor_vec"))
+                amap = torch.empty((env.E, env.A, 6, H, W), **f) if R is None else \
+                    env.ego_buffers(R, dtype=self.ego_dtype)
+                self._obs = dict(actor_map=amap, actor_vec=torch.empty((env.E, env.A, env.actor_vec_dim), **f))
+            if R is None:
+                env.build_obs(out=self._obs, which=("actor_map", "actor_vec"))
+            else:
+                env.build_obs(out=self._obs, which=("actor_vec",))
+                env.build_obs_ego(R, out=self._obs["actor_map"], dtype=self.ego_dtype)
             if self._masked and self.avail is None:
                 self.avail = torch.ones((env.E, env.A, ACTION_DIM), dtype=torch.uint8, device=env.device)
 
@@ -227,8 +244,13 @@ class Evaluator(Graphed):
                 else:
                     sample_actions(logits, self.seed, self.offset, out=(acts, self._log_probs), avail=av)
                     self.offset += 1
-                env.step_episode(self.actions, self.active, action_format="int", obs_out=self._obs,
-                                 which=("actor_map", "actor_vec"))
+                if self.ego_radius is None:
+                    env.step_episode(self.actions, self.active, action_format="int", obs_out=self._obs,
+                                     which=("actor_map", "actor_vec"))
+                else:
+                    env.step_episode(self.actions, self.active, action_format="int", filled=self.filled,
+                                     obs_out=self._obs, which=("actor_vec",))
+                    env.build_obs_ego_masked(self.ego_radius, self.filled, out=om, dtype=self.ego_dtype)
         if dev_offset and kind == "policy" and not deterministic:
             check(lib().mdl_counter_add(ptr(self._off_dev), n, stream_handle(env.device)), "mdl_counter_add")
 
@@ -237,7 +259,8 @@ class Evaluator(Graphed):
 
 
 def run_eval(agent_type: str, env_config: dict, num_episodes: int, policy=None, deterministic: bool | None = None,
-             agent_seed: int | None = None, graph: bool = False) -> dict:
+             agent_seed: int | None = None, graph: bool = False, ego_radius: int | None = None,
+             ego_dtype: torch.dtype = torch.float32) -> dict:
     """``evaluation.run_eval`` (evaluation.py:9-66) with the ``num_episodes`` episodes as the envs of
     one ``BatchedEnv``: env ``ep`` is seeded ``env_config['seed'] + ep``, tracker "fresh".
     env_config: map, max_time_steps, n_agents, n_packages, seed (evaluation.py:94-100).
@@ -245,7 +268,8 @@ def run_eval(agent_type: str, env_config: dict, num_episodes: int, policy=None, 
     defaulting to env_config['seed'] as evaluation.py:80 seeds numpy; raises RuntimeError if an
     episode ended before max_time_steps, because the reference's stream would then be shorter for
     that episode and the tape would no longer line up); "mappo" (``policy``, sampled unless
-    ``deterministic`` is given: evaluation.py:40-42).  Returns the reference's result dict."""
+    ``deterministic`` is given: evaluation.py:40-42).  ego_radius / ego_dtype: the policy takes actor-map
+    windows (``Evaluator``).  Returns the reference's result dict."""
     from .engine import BatchedEnv
     if agent_type not in ("greedy", "random", "mappo"):
         raise ValueError(f"Unknown agent type: {agent_type}")
@@ -259,7 +283,7 @@ def run_eval(agent_type: str, env_config: dict, num_episodes: int, policy=None, 
     env = BatchedEnv(env_config["map"], E, int(env_config["n_agents"]), int(env_config["n_packages"]), T,
                      seeds=[base + ep for ep in range(E)], tracker="fresh")
     try:
-        ev = Evaluator(env, seed=seed)
+        ev = Evaluator(env, seed=seed, ego_radius=ego_radius, ego_dtype=ego_dtype)
         if agent_type == "greedy":
             ev.run("greedy", graph=graph)
         elif agent_type == "random":

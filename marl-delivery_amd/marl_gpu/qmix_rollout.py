@@ -30,7 +30,8 @@ class QmixCollector(Graphed):
     with ``agent.init_hidden()`` -> [1, Hd] as the reference's ``AgentNetwork``.
 
     Time-major buffers, L = min(episode_limit, env.T):
-      so [L+1, E, A, 6, H, W], vo [L+1, E, A, Dv], gs [L+1, E, 4, H, W], gv [L+1, E, Dg]
+      so [L+1, E, A, 6, H, W] (with ego_radius: [L+1, E, A, 6, K, K], below), vo [L+1, E, A, Dv],
+      gs [L+1, E, 4, H, W], gv [L+1, E, Dg]
       (slot t = the observations before step t, slot t+1 = after it), u uint8 [L, E, A],
       r float32 [L, E] (the fp64 global reward rounded once, as the reference's float32
       buffer does; r64 keeps the fp64 values), r_shaped float32 [L, E], terminated and
@@ -45,12 +46,23 @@ class QmixCollector(Graphed):
     has ended: every slot is written).  ``EpisodeReplay`` stores it and returns it as avail_u /
     avail_u_next.  avail=False (the default): nothing changes.
 
+    ego_radius=R (1..15, K = 2R + 1): the agent sees each robot's K x K window of its actor map
+    (``BatchedEnv.build_obs_ego``) instead of the full map: so is [L+1, E, A, 6, K, K] of ``ego_dtype``
+    (torch.float32, float16 or bfloat16) and the agent is called with so [E*A, 6, K, K] in that type.
+    vo, gs, gv stay float32 and the mixer's state keeps the full map (so the envs still share one map
+    shape).  Each step is then two launches: ``step_episode`` writes vo / gs / gv, and
+    ``build_obs_ego_masked`` under that step's ``filled`` writes the windows of the envs that were
+    stepped -- ``filled``, not ``active``, which is already cleared for an env that finished on this
+    step while its terminal observation is still due, as the full-map path writes it.  Rows past an
+    episode's end stay unwritten, as in the full-map form.  ego_radius=None (the default): nothing changes.
+
     One deviation from the reference: the agent also runs on the finished envs (the
     reference shrinks its batch instead).  Their actions and hidden states are ignored --
     the engine does not step them -- so the finished envs cost forward-pass time only.
     """
 
-    def __init__(self, env, episode_limit: int, seed: int = 0, avail: bool = False):
+    def __init__(self, env, episode_limit: int, seed: int = 0, avail: bool = False, ego_radius: int | None = None,
+                 ego_dtype: torch.dtype = torch.float32):
         self.env = env
         self.L = L = min(int(episode_limit), env.T)
         if L < 1:
@@ -62,7 +74,14 @@ class QmixCollector(Graphed):
         dev = env.device
         f = dict(dtype=torch.float32, device=dev)
         b = dict(dtype=torch.uint8, device=dev)
-        self.so = torch.zeros((L + 1, E, A, 6, H, W), **f)
+        self.ego_radius = None if ego_radius is None else env._ego_radius(ego_radius)
+        self.ego_dtype = ego_dtype
+        if self.ego_radius is None:
+            self.so = torch.zeros((L + 1, E, A, 6, H, W), **f)
+        else:
+            K = 2 * self.ego_radius + 1
+            env.ego_buffers(self.ego_radius, 0, ego_dtype)   # raises on a dtype the builder does not write
+            self.so = torch.zeros((L + 1, E, A, 6, K, K), dtype=ego_dtype, device=dev)
         self.vo = torch.zeros((L + 1, E, A, env.actor_vec_dim), **f)
         self.gs = torch.zeros((L + 1, E, 4, H, W), **f)
         self.gv = torch.zeros((L + 1, E, env.critic_vec_dim), **f)
@@ -80,6 +99,8 @@ class QmixCollector(Graphed):
         self.avail = torch.ones((L + 1, E, A, ACTION_DIM), **b) if avail else None
 
     def _slot(self, k):
+        if self.ego_radius is not None:   # so[k] holds windows: build_obs_ego's, not the builders'
+            return dict(actor_vec=self.vo[k], critic_map=self.gs[k], critic_vec=self.gv[k])
         return dict(actor_map=self.so[k], actor_vec=self.vo[k], critic_map=self.gs[k], critic_vec=self.gv[k])
 
     def batch(self):
@@ -126,7 +147,12 @@ class QmixCollector(Graphed):
         if env.tracker != "fresh":
             env.clear_tracker()
         self.active.fill_(1)
-        env.build_obs(out=self._slot(0))
+        R = self.ego_radius
+        which = ("actor_map", "actor_vec", "critic_map", "critic_vec") if R is None else \
+            ("actor_vec", "critic_map", "critic_vec")
+        env.build_obs(out=self._slot(0), which=which)
+        if R is not None:
+            env.build_obs_ego(R, out=self.so[0], dtype=self.ego_dtype)
         masks = self.avail
         if masks is not None:
             env.avail_actions(self.active, out=masks[0])
@@ -145,7 +171,9 @@ class QmixCollector(Graphed):
                 select_actions_eps(q, epsilon, self.seed, self.offset, avail=av, out=self.u[t].view(-1))
             self.offset += 1
             env.step_episode(self.u[t], self.active, out=(self.r64[t], self.r_shaped[t], self.terminated[t]),
-                             filled=self.filled[t], obs_out=self._slot(t + 1))
+                             filled=self.filled[t], obs_out=self._slot(t + 1), which=which)
+            if R is not None:   # the envs this step moved, those that just finished included
+                env.build_obs_ego_masked(R, self.filled[t], out=self.so[t + 1], dtype=self.ego_dtype)
             if masks is not None:
                 env.avail_actions(self.active, out=masks[t + 1])
         if dev_args:

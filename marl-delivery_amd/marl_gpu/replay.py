@@ -180,7 +180,10 @@ class EpisodeReplay:
     ``collector``: a ``QmixCollector`` or one of its batches (a dict with so, vo, gs, gv, u, r,
     terminated, filled) -- the template for shapes, dtypes and device.  A template with an
     ``avail`` field (uint8 [L+1, E, A, n_actions], ``QmixCollector(avail=True)``) makes the ring
-    store the valid-action masks too (``self.fields``; ``FIELDS`` is the reference's set).
+    store the valid-action masks too (``self.fields``; ``FIELDS`` is the reference's set).  A window-form
+    template (``QmixCollector(ego_radius=R, ego_dtype=...)``) gives a ring whose so is
+    [L+1, capacity, A, 6, K, K] of that dtype, and ``sample`` returns so / so_next [B, L, A, 6, K, K] in
+    it: nothing here depends on the map's shape or on float32.
 
     ``add`` stores a batch's E episodes in env order; the reference stores each episode when it
     terminates, i.e. in termination order.  Only the eviction order inside one batch differs.

@@ -12,6 +12,10 @@
                     and the half types in one process; rollout / rollout_graph collect in that type
   --ego-radius      R (or several): configs 3 / 5 time build_obs_ego (float32 and bfloat16, all envs in one
                     call) beside the full actor maps' build_obs in one process
+  --ego-active      FRACTION (or several), with --ego-radius: also time build_obs_ego_masked under a fixed
+                    mask with that share of the envs set (1 = all set: the mask's own cost)
+  --ego-collect     E, with --ego-radius and --config 5: one QmixCollector(ego_radius=R).collect(graph=True)
+                    of E envs on config 5's shape with a linear agent, instead of the builder's times
   --config alt      IDQ/qmix featurizers (§8(f)2)
   --config greedy   batched greedy baseline (§8(f)3)
   --qmix            QMIX episode collection: the masked step against the full step, and one collector
@@ -234,12 +238,20 @@ def run_obs_dtype(cfg, steps, warmup, names, rounds=3):
     env.close()
 
 
-def run_ego(cfg, radii, steps, warmup, rounds=3):
+def ego_mask(E, frac):
+    """A fixed mask with the share `frac` of E envs set, spread evenly: env e is set where floor((e + 1) * frac)
+    passes floor(e * frac) (1/2: every second env, 1/8: every eighth)."""
+    e = np.arange(E, dtype=np.int64)
+    return (np.floor((e + 1) * frac + 1e-9) > np.floor(e * frac + 1e-9)).astype(np.uint8)
+
+
+def run_ego(cfg, radii, steps, warmup, rounds=3, active=()):
     """Robot-centred actor-map windows ("Egocentric actor windows"), config 3 or 5: in one
     process, on one engine, ``build_obs_ego`` over all of the rank's envs in one call, float32 and
     bfloat16 at each radius, beside the existing full-map ``build_obs(which=("actor_map",))`` (float32;
     config 5: per chunk of 4,096 envs, as its usual leg builds them).  Every figure is a hipGraph of 10
-    captured calls, each graph captured once and replayed in turn, ``rounds`` times."""
+    captured calls, each graph captured once and replayed in turn, ``rounds`` times.  ``active``: shares of
+    the envs; for each, ``build_obs_ego_masked`` under ``ego_mask`` is timed the same way."""
     import marl_gpu
     from marl_gpu.maps import grid_array, load_map, map_path
     dev = torch.device("cuda", 0)
@@ -279,6 +291,16 @@ def run_ego(cfg, radii, steps, warmup, rounds=3):
                     env.build_obs_ego(R, out=buf, dtype=OBS_DTYPES[n])
 
             graphs[f"ego_r{R}_{n}"] = (_graph_of(ego_), buf, buf.numel() * buf.element_size())
+            for frac in active:
+                rows = torch.from_numpy(ego_mask(E, frac)).to(dev)
+                nset = int(rows.sum())
+
+                def masked_(buf=buf, R=R, n=n, rows=rows):
+                    for k in range(C):
+                        env.build_obs_ego_masked(R, rows, out=buf, dtype=OBS_DTYPES[n])
+
+                graphs[f"ego_r{R}_{n}_masked_{frac:g}"] = (_graph_of(masked_), (buf, rows),
+                                                           buf.numel() * buf.element_size() // E * nset)
     reps = max(1, steps // 50)
     t = {k: [] for k in graphs}
     for _ in range(rounds):
@@ -288,10 +310,59 @@ def run_ego(cfg, radii, steps, warmup, rounds=3):
     for k, (_, _, b) in graphs.items():
         best = min(t[k])
         res[k] = {"us_per_call": t[k], "envs_per_call": chunk if k.startswith("full") else E, "bytes_written": b,
+                  **({"envs_set": int(graphs[k][1][1].sum())} if "_masked_" in k else {}),
                   "achieved_GBs": b / (best * 1e-6) / 1e9, "frac_of_8TBs": b / (best * 1e-6) / 1e9 / HBM}
     res["full_map_float32"]["us_all_envs"] = [x * nchunks for x in t["full_map_float32"]]
     print(json.dumps({"config": cfg + ":ego", "envs": E, "agents": A, "packages": P, "map": [H, H], "radii": list(radii),
                       "rounds": rounds, "replays": reps, "calls_per_graph": C, "builds": res}), flush=True)
+    env.close()
+
+
+def run_ego_collect(E, R, steps):
+    """One ``QmixCollector(ego_radius=R).collect(graph=True)`` on config 5's shape (synthetic 64x64, A = 16,
+    P = 100, T = 500) at E envs, with a linear agent on the actor vector: us per env-step of whole collects
+    (every env counted for all L steps, as the loop runs them)."""
+    import marl_gpu
+    from marl_gpu.maps import grid_array, load_map, map_path
+    from marl_gpu.qmix_rollout import QmixCollector
+    dev = torch.device("cuda", 0)
+    A, P, T = 16, 100, 500
+    env = marl_gpu.BatchedEnv(grid_array(load_map(map_path("synthetic64.txt"))), E, A, P, T, seed=7, tracker="fresh",
+                              shaping="qmix", max_other_robots=15, max_packages_obs=20, max_robots_state=16,
+                              max_packages_state=100)
+    gen = torch.Generator(device=dev).manual_seed(0)
+    w = torch.randn(env.actor_vec_dim, 15, device=dev, generator=gen)
+    h0 = torch.zeros(1, 4, device=dev)
+
+    class Agent:
+        def init_hidden(self):
+            return h0
+
+        def __call__(self, so, vo, h):
+            return vo @ w, h
+
+    ag = Agent()
+    out = {}
+    for name, dt in (("float32", torch.float32), ("bfloat16", torch.bfloat16)):
+        col = QmixCollector(env, T, seed=1, ego_radius=R, ego_dtype=dt)
+        col.collect(ag, 0.05, graph=True)   # eager, then the capture
+        n = max(2, steps // 100)
+        times = []
+        for _ in range(3):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(n):
+                col.collect(ag, 0.05, graph=True)
+            torch.cuda.synchronize()
+            times.append((time.perf_counter() - t0) / n)
+        out[name] = {"ms_per_collect": [x * 1e3 for x in times],
+                     "us_per_env_step": [x * 1e6 / (E * col.L) for x in times],
+                     "us_per_step": [x * 1e6 / col.L for x in times],
+                     "so_bytes": col.so.numel() * col.so.element_size(),
+                     "mean_episode_length": float(col.episode_length.double().mean())}
+        del col
+    print(json.dumps({"config": "5:ego_collect", "envs": E, "agents": A, "packages": P, "map": [64, 64], "radius": R,
+                      "L": T, "collects_per_round": n, "rounds": 3, "collect": out}), flush=True)
     env.close()
 
 
@@ -1152,10 +1223,19 @@ def main():
                     help="a radius in 1..15 (or several, comma-separated): configs 3 / 5 print the window builder's "
                          "times (build_obs_ego, float32 and bfloat16) beside the full actor maps' instead of their "
                          "usual line")
+    ap.add_argument("--ego-active", default="",
+                    help="with --ego-radius: a share of the envs in (0, 1] (or several, comma-separated); also time "
+                         "build_obs_ego_masked under a fixed mask with that share set")
+    ap.add_argument("--ego-collect", type=int, default=0,
+                    help="with --ego-radius and --config 5: time QmixCollector(ego_radius=R).collect(graph=True) at "
+                         "this many envs instead of the builder (one radius, no --ego-active)")
     a = ap.parse_args()
     radii = [int(x) for x in a.ego_radius.split(",") if x]
     if any(not 1 <= r <= 15 for r in radii):
         ap.error(f"--ego-radius: {a.ego_radius!r} (1..15)")
+    active = [float(x) for x in a.ego_active.split(",") if x]
+    if any(not 0.0 < f <= 1.0 for f in active) or (active and not radii):
+        ap.error(f"--ego-active: {a.ego_active!r} (shares in (0, 1], with --ego-radius)")
     obs_dtypes = a.obs_dtype.split(",")
     if any(n not in OBS_DTYPES for n in obs_dtypes):
         ap.error(f"--obs-dtype: {a.obs_dtype!r} (float32, float16, bfloat16)")
@@ -1186,8 +1266,12 @@ def main():
             run_alt(a.steps)
         elif c == "greedy":
             run_greedy(a.steps)
+        elif radii and a.ego_collect:
+            if c != "5" or len(radii) != 1 or active:
+                ap.error("--ego-collect goes with --config 5 and one --ego-radius, without --ego-active")
+            run_ego_collect(a.ego_collect, radii[0], a.steps)
         elif radii:
-            run_ego(c, radii, a.steps, a.warmup)
+            run_ego(c, radii, a.steps, a.warmup, active=active)
         elif c in ("3", "3b") and half:
             run_obs_dtype(c, a.steps, a.warmup, half)
         else:
