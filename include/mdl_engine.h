@@ -544,6 +544,29 @@ int mdl_build_obs_ego(MdlEngine* eng, int32_t env_begin, int32_t n, int32_t radi
 int mdl_build_obs_ego_masked(MdlEngine* eng, int32_t env_begin, int32_t n, const uint8_t* rows, int32_t radius,
                              int32_t dtype, void* actor_ego, void* stream);
 
+/* Robot-centred windows of the IDQ / map-QMIX agent observation (no reference counterpart: a crop of
+ * convert_state's tensor, IDQ/networks.py:112-217 == qmix/networks.py:243-348).  For radius R = `radius` in
+ * [1, MDL_EGO_MAX_RADIUS] and K = 2R + 1, robot a on 0-based cell (r, c):
+ *   idq_ego [n][A][6][K][K] float32,  idq_ego[a][ch][i][j] = idq_obs[a][ch][r - R + i][c - R + j]
+ * where that cell lies inside the env's map (idq_obs: exactly what mdl_build_obs_alt writes for the same
+ * state, tracker mode and clock); outside the map channel 0 is 1.0 and channels 1-5 are 0.0.  Channel 4 is
+ * therefore a single 1.0 at (R, R); channel 1 holds the same float32 urgency bits as the full tensor; a
+ * carrying robot has all-zero channels 1 and 2; the carried id's target (channel 5) may lie outside the
+ * window.  The output is float32 only: the urgency plane would not survive a half type exactly, and the
+ * replay rings (mdl_replay_append*) take float rows -- there is no half form of these windows.
+ * rows: NULL (every env of the range), or DEVICE uint8 [E] indexed by ENV ID (rows[e] for env e of
+ * [env_begin, env_begin + n), not by the output row e - env_begin); non-zero = build.  The output row of
+ * env e is idq_ego + (e - env_begin) * A * 6 * K * K elements either way; rows of unmarked envs are not
+ * written, not one byte.  The mask is read on the device by the launch itself.
+ * The output shape does not depend on the map, so the range is checked against [0, E) only and may cross
+ * map shapes (mdl_build_obs_alt refuses that).  Asynchronous on `stream`, no host round trip: the call can
+ * be captured in a hipGraph.  n == 0 succeeds and launches nothing.  A radius outside
+ * [1, MDL_EGO_MAX_RADIUS], a null idq_ego with n > 0 or an LDS slice that does not fit fail with a message
+ * and leave the engine usable.  mdl_step_episode, the dict-API helpers and the views entry points
+ * (mdl_views_alt_features) have no window form. */
+int mdl_build_obs_alt_ego(MdlEngine* eng, int32_t env_begin, int32_t n, const uint8_t* rows /* NULL: every env */,
+                          int32_t radius, float* idq_ego, void* stream);
+
 /* State snapshot into caller DEVICE buffers (async on `stream`).  Any pointer may be NULL.
  *   robots   int32 [E][A][3]  (row, col, carrying), 0-indexed
  *   pkgs     int32 [E][P][8]  (sr, sc, tr, tc, start_time, deadline, id, status 0 None/1 waiting/2 in_transit/3 delivered)

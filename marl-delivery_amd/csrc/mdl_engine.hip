@@ -1139,6 +1139,25 @@ int mdl_build_obs_ego_masked(MdlEngine* eng, int32_t env_begin, int32_t n, const
     return build_obs_ego("mdl_build_obs_ego_masked", eng, env_begin, n, rows, radius, dtype, actor_ego, stream);
 }
 
+int mdl_build_obs_alt_ego(MdlEngine* eng, int32_t env_begin, int32_t n, const uint8_t* rows, int32_t radius,
+                          float* idq_ego, void* stream) {
+    const char* who = "mdl_build_obs_alt_ego";
+    if (!eng) return fail("%s: null engine", who);
+    if (radius < 1 || radius > MDL_EGO_MAX_RADIUS)
+        return fail("%s: radius %d outside [1, %d]", who, radius, MDL_EGO_MAX_RADIUS);
+    // any envs of [0, E): the windows have one shape whatever the maps, each wave reads its own env's
+    if (env_begin < 0 || n < 0 || env_begin + n > eng->p.E) return fail("%s: env range out of bounds", who);
+    if (n == 0) return 0;
+    if (!idq_ego) return fail("%s: null output", who);
+    const int G = mdl::alt_ego_group(eng->p.A, eng->p.P, eng->maxHW, radius, LDS_BUDGET);
+    if (G < 1) return fail("%s: the windows need more than %zu bytes of LDS per env", who, LDS_BUDGET);
+    const size_t lds = mdl::alt_ego_lds(eng->p.A, eng->p.P, eng->maxHW, G, radius);
+    DeviceGuard dg(eng->device);
+    HIPCHK(mdl::launch_alt_ego(eng->p, env_begin, n, rows, radius, idq_ego, waves_per_block(lds), lds, G,
+                               (hipStream_t)stream));
+    return 0;
+}
+
 int mdl_read_state(MdlEngine* eng, int32_t* robots, int32_t* pkgs, int32_t* t, double* total_reward,
                    int32_t* tracker, int32_t* tracker_data, void* stream) {
     if (!eng) return fail("mdl_read_state: null engine");

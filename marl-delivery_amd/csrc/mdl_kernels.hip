@@ -1465,6 +1465,8 @@ __global__ __launch_bounds__(256) void k_obs_h(DevParams p, int env_begin, int n
 
 // robot-centred actor-map windows (k_ego_maps), on the tracker staging above
 #include "mdl_ego.hpp"
+// the same windows of the IDQ / map-QMIX agent observation (k_alt_ego), on mdl_ego.hpp's bit helpers
+#include "mdl_alt_ego.hpp"
 
 // ------------------------------------------------------ dict views (helpers)
 // record: [t, A, n_slots, map] + A*(r, c, carry) + n_slots*(id, status, sr, sc, tr, tc, st, dl)
@@ -2514,6 +2516,29 @@ hipError_t launch_ego(const DevParams& p, int env_begin, int n, const uint8_t* r
         if (dtype == OBS_F32) go(st, float{});
         else if (dtype == OBS_F16) go(st, f16_t{});
         else go(st, bf16_t{});
+    });
+    return hipGetLastError();
+}
+
+// ---- the IDQ window builder (mdl_alt_ego.hpp) ----
+// Robots per image, as ego_group on this kernel's fixed part of the slice; 0 if not even one robot's fits.
+int alt_ego_group(int A, int P, int maxHW, int R, size_t budget) {
+    const int K = 2 * R + 1;
+    const size_t fixed = alt_ego_fixed_bytes(A, P, maxHW);
+    if (fixed >= budget) return 0;
+    const size_t room = budget - fixed < (size_t)EGO_IMAGE_BYTES ? budget - fixed : (size_t)EGO_IMAGE_BYTES;
+    int G = A;
+    while (G > 0 && align16(sizeof(uint32_t) * (size_t)ego_image_words(G, K)) > room) G--;
+    return G;
+}
+size_t alt_ego_lds(int A, int P, int maxHW, int G, int R) { return alt_ego_lds_bytes(A, P, maxHW, G, 2 * R + 1); }
+
+hipError_t launch_alt_ego(const DevParams& p, int env_begin, int n, const uint8_t* rows, int R, float* out, int wpb,
+                          size_t lds, int G, hipStream_t s) {
+    if (R < 1 || R > EGO_RMAX || G < 1 || wpb < 1) return hipErrorInvalidValue;
+    with_int<0, 1>(p.stale != 0, [&](auto st) {
+        hipLaunchKernelGGL(k_alt_ego<decltype(st)::value != 0>, dim3(blocks_for(n, wpb)), dim3(256), lds * wpb, s, p,
+                           env_begin, n, R, out, wpb, (int)lds, G, rows);
     });
     return hipGetLastError();
 }

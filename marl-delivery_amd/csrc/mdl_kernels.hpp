@@ -75,6 +75,12 @@ size_t ego_lds(int P, int maxHW, int G, int R);
 // rows of the other envs stay unwritten (k_masked_ego_maps); null: every env of the range (k_ego_maps).
 hipError_t launch_ego(const DevParams& p, int env_begin, int n, const uint8_t* rows, int R, int dtype, void* out,
                       int wpb, size_t lds, int G, hipStream_t s);
+// The same windows of k_alt_obs's idq_obs (k_alt_ego, mdl_alt_ego.hpp): float32 out [n][A][6][K][K];
+// rows as launch_ego's (null: every env of the range).  alt_ego_group / alt_ego_lds as ego_group / ego_lds.
+int alt_ego_group(int A, int P, int maxHW, int R, size_t budget);
+size_t alt_ego_lds(int A, int P, int maxHW, int G, int R);
+hipError_t launch_alt_ego(const DevParams& p, int env_begin, int n, const uint8_t* rows, int R, float* out, int wpb,
+                          size_t lds, int G, hipStream_t s);
 // A launch's own completion word (host-mapped): every wave of its grid counts itself in the
 // running device counter `ctr` (never reset: `base` is its value before the launch) after a
 // system-scope release of its stores; the last one writes `value` to `seq`.  seq == nullptr: none;

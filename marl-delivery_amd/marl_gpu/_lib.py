@@ -92,6 +92,7 @@ SIGNATURES = {
     "mdl_build_obs_ego": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "mdl_build_obs_ego_masked": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp]),
     "mdl_build_obs_alt": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp]),
+    "mdl_build_obs_alt_ego": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _vp, _vp]),
     "mdl_alt_pre_bytes": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
     "mdl_alt_transition": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "mdl_views_alt_features": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp]),

@@ -637,6 +637,49 @@ class BatchedEnv:
         check(lib().mdl_build_obs_alt(self._h, env_begin, n, *op, self._stream()), "mdl_build_obs_alt")
         return out
 
+    def build_obs_alt_ego(self, radius: int, env_begin: int = 0, n: int | None = None,
+                          rows: torch.Tensor | None = None, out: torch.Tensor | None = None):
+        """Each robot's ``K x K`` window of its ``idq_obs`` (``build_obs_alt``: convert_state), centred on
+        the robot (K = 2 * radius + 1, radius in 1..15), for envs [env_begin, env_begin + n): a float32
+        tensor [n, A, 6, K, K].
+
+        ``ego[e, a, ch, i, j] = build_obs_alt()["idq_obs"][e, a, ch, r - radius + i, c - radius + j]`` for
+        robot a on cell (r, c) where that cell lies inside the map -- same tracker mode and clock, channel
+        1 the same float32 urgency bits.  Outside the map channel 0 is 1.0 and channels 1-5 are 0.0, so
+        channel 4 is a single 1.0 at (radius, radius).  A carrying robot's channels 1 and 2 are zero, and
+        its carried target (channel 5) may fall outside the window.  The shape does not depend on the
+        map, so the range may cross map shapes (``build_obs_alt`` refuses that).
+
+        float32 only: the urgency plane would not survive a half type exactly and the replay rings hold
+        float rows; these windows have no half form.
+
+        ``rows``: None, or uint8 [E] on the engine's device, indexed by env id whatever the range; a
+        non-zero byte = build.  The launch reads the mask itself (no host round trip, so the call can be
+        captured in a hipGraph).  The rows of unmarked envs are not written -- in a caller's ``out`` they
+        keep what they held, and a fresh tensor (``out=None``) starts as zeros.  ``out``: a contiguous
+        float32 tensor on the engine's device with n * A * 6 * K * K entries."""
+        R = self._ego_radius(radius)
+        K = 2 * R + 1
+        if rows is not None:
+            self._check_mask(rows, "rows")
+        env_begin = int(env_begin)
+        n = self.E - env_begin if n is None else int(n)
+        if env_begin < 0 or n < 0 or env_begin + n > self.E:
+            raise IndexError(f"env range [{env_begin}, {env_begin + n}) outside [0, {self.E})")
+        need = n * self.A * 6 * K * K
+        if out is None:
+            make = torch.empty if rows is None else torch.zeros
+            out = make((n, self.A, 6, K, K), dtype=torch.float32, device=self.device)
+        else:
+            self._check_buf(out, torch.float32, need, (TypeError, "out must be a float32 tensor"),
+                            (ValueError, f"out must be contiguous on {self.device}"),
+                            (ValueError, f"out holds {{n}} entries, needs {need} ({n}, {self.A}, 6, {K}, {K})"))
+        if n == 0:
+            return out
+        check(lib().mdl_build_obs_alt_ego(self._h, env_begin, n, ptr(rows), R, ptr(out), self._stream()),
+              "mdl_build_obs_alt_ego")
+        return out
+
     def alt_pre_buffer(self) -> torch.Tensor:
         """The pre-record of ``alt_transition`` (uint8, ``mdl_alt_pre_bytes`` long): what
         reward_shaping reads of the state and the tracker from before a step."""

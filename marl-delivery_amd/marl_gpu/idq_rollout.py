@@ -28,7 +28,8 @@ class IdqCollector(Graphed):
     from the reset state (IDQ/trainer.py:235-239), which is the reset's own tracker update on an
     empty tracker.  (Cleared after the reset, the packages that start at t = 0 would never be
     inserted: the update inserts a package at its start time only.)
-    replay: a ``TransitionReplay`` with obs_shape (6, H, W) on the env's device.
+    replay: a ``TransitionReplay`` with obs_shape (6, H, W) on the env's device ((6, K, K) with
+    ``ego_radius``).
     agent(obs [E*A, 6, H, W]) -> q [E*A, n_actions], as the reference's ``AgentNetwork``.
     ops_are_ints=False reproduces the trainer, which hands reward_shaping string ops (only the
     stay penalty fires); True gives reward_shaping the integer ops its branches test for.
@@ -40,15 +41,24 @@ class IdqCollector(Graphed):
     One deviation from the reference: its plain ``VectorizedEnv`` keeps stepping finished envs
     with stay actions and ignores the results; here they are not stepped.  Nothing the trainer
     consumes differs (the agent still runs on their stale observation rows: forward time only).
+
+    ego_radius=R (1..15): the observations are each robot's ``K x K`` window (K = 2R + 1) of its
+    convert_state tensor (``BatchedEnv.build_obs_alt_ego``, float32) instead of the whole map: the
+    replay must hold (6, K, K) observations, ``obs`` is [2, E, A, 6, K, K] and the agent receives
+    [E*A, 6, K, K].  Rewards, actions and the ring's other columns are those of the full-map form.
     """
 
-    def __init__(self, env, replay: TransitionReplay, seed: int = 0, ops_are_ints: bool = False):
+    def __init__(self, env, replay: TransitionReplay, seed: int = 0, ops_are_ints: bool = False,
+                 ego_radius: int | None = None):
         self.env, self.replay = env, replay
         self.seed = int(seed)
         self.ops_are_ints = bool(ops_are_ints)
+        self.ego_radius = None if ego_radius is None else env._ego_radius(ego_radius)
         self._init_graphs(env.device)
         E, A = env.E, env.A
         H, W = env.single_map_shape("IdqCollector")
+        if self.ego_radius is not None:
+            H = W = 2 * self.ego_radius + 1
         if replay.obs_shape != (6, H, W) or replay.cursor.device != env.device:
             raise ValueError(f"IdqCollector: replay must hold (6, {H}, {W}) observations on {env.device}")
         dev = env.device
@@ -74,7 +84,11 @@ class IdqCollector(Graphed):
         env.reset()
         self.active.fill_(1)
         self.cur = 0
-        env.alt_transition(None, self.pre, out={"idq_obs": self.obs[0]})
+        if self.ego_radius is None:
+            env.alt_transition(None, self.pre, out={"idq_obs": self.obs[0]})
+        else:
+            env.alt_transition(None, self.pre, which=())
+            env.build_obs_alt_ego(self.ego_radius, out=self.obs[0])
 
     def _step(self, agent, epsilon, dev_args, k):
         env = self.env
@@ -88,8 +102,13 @@ class IdqCollector(Graphed):
         self.offset += 1
         env.step_episode(self.u, self.active, out=(self.r_env, self.r_shaped, self.done), filled=self.filled,
                          obs_out={}, which=())
-        env.alt_transition(self.u, self.pre, row_mask=self.filled, ops_are_ints=self.ops_are_ints,
-                           out={"idq_obs": o2}, r_out=self.r_idq)
+        if self.ego_radius is None:
+            env.alt_transition(self.u, self.pre, row_mask=self.filled, ops_are_ints=self.ops_are_ints,
+                               out={"idq_obs": o2}, r_out=self.r_idq)
+        else:
+            env.alt_transition(self.u, self.pre, row_mask=self.filled, ops_are_ints=self.ops_are_ints, which=(),
+                               r_out=self.r_idq)
+            env.build_obs_alt_ego(self.ego_radius, rows=self.filled, out=o2)
         self.replay.add(self.filled, o, self.u, self.r_idq, o2, self.done)
         self.cur = 1 - self.cur
 

@@ -27,7 +27,8 @@ class QmixCycleCollector(Graphed):
 
     env: a ``BatchedEnv`` whose envs share one map shape, tracker="fresh" or a stale tracker (which
     the lazy reset empties, as the trainer replaces ``persistent_packages`` by ``{}``).
-    replay: a ``JointReplay`` with obs_shape (6, H, W) and state_shape (7, h, w) on the env's device.
+    replay: a ``JointReplay`` with obs_shape (6, H, W) ((6, K, K) with ``ego_radius``) and state_shape
+    (7, h, w) on the env's device.
     hidden_dim None: ``agent(obs [E*A, 6, H, W]) -> q [E*A, n_actions]``.  Otherwise the agent is
     recurrent, ``agent(obs, hidden [E*A, hidden_dim]) -> (q, new_hidden)``; the reference's ``None``
     hidden state is the zero row here.
@@ -39,14 +40,24 @@ class QmixCycleCollector(Graphed):
     outer loop for all envs (the caller trains between steps); ``cycle`` runs several.  Env state,
     ``done`` and the hidden state carry over between steps and cycles, as in the reference.  Nothing
     in ``step`` synchronises with the host.
+
+    ego_radius=R (1..15): the agents' observations are each robot's ``K x K`` window (K = 2R + 1) of its
+    convert_state tensor (``BatchedEnv.build_obs_alt_ego``, float32) instead of the whole map: the
+    replay must hold (6, K, K) observations, ``obs`` is [2, E, A, 6, K, K] and the agent receives
+    [E*A, 6, K, K].  The state keeps its (7, h, w); everything but the observations is the full-map
+    form's.
     """
 
-    def __init__(self, env, replay: JointReplay, seed: int = 0, hidden_dim: int | None = None):
+    def __init__(self, env, replay: JointReplay, seed: int = 0, hidden_dim: int | None = None,
+                 ego_radius: int | None = None):
         self.env, self.replay = env, replay
         self.seed = int(seed)
+        self.ego_radius = None if ego_radius is None else env._ego_radius(ego_radius)
         self._init_graphs(env.device)
         E, A = env.E, env.A
         H, W = env.single_map_shape("QmixCycleCollector")
+        if self.ego_radius is not None:
+            H = W = 2 * self.ego_radius + 1
         ss = replay.state_shape
         if replay.obs_shape != (6, H, W) or len(ss) != 3 or ss[0] != 7 or replay.n_agents != A \
                 or replay.cursor.device != env.device:
@@ -82,19 +93,34 @@ class QmixCycleCollector(Graphed):
             env.clear_tracker()   # before the reset, whose tracker update then inserts the t = 0 packages
         env.reset()
         self.cur = 0
-        env.build_obs_alt(out={"idq_obs": self.obs[0], "qmix_state": self.state[0]}, state_shape=self.state_shape)
+        self._observe(self.obs[0], self.state[0])
         if self.hidden is not None:
             self.hidden.zero_()
         self.done.zero_()
+
+    def _observe(self, o, s):
+        """Every env's observations (whole maps, or the windows) and state into o, s."""
+        env = self.env
+        if self.ego_radius is None:
+            env.build_obs_alt(out={"idq_obs": o, "qmix_state": s}, state_shape=self.state_shape)
+        else:
+            env.build_obs_alt(out={"qmix_state": s}, state_shape=self.state_shape, which=("qmix_state",))
+            env.build_obs_alt_ego(self.ego_radius, out=o)
 
     def _step(self, agent, epsilon, dev_args, k, completed, completed_return):
         env = self.env
         E, A = env.E, env.A
         c = self.cur
         o, o2, s, s2 = self.obs[c], self.obs[1 - c], self.state[c], self.state[1 - c]
-        env.cycle_begin(self.done, out={"idq_obs": o, "qmix_state": s}, completed=completed,
-                        completed_return=completed_return, completed_steps=self.completed_steps,
-                        state_shape=self.state_shape)
+        if self.ego_radius is None:
+            env.cycle_begin(self.done, out={"idq_obs": o, "qmix_state": s}, completed=completed,
+                            completed_return=completed_return, completed_steps=self.completed_steps,
+                            state_shape=self.state_shape)
+        else:   # the reset envs' state from the lazy reset's launch, their windows under its `completed`
+            env.cycle_begin(self.done, out={"qmix_state": s}, completed=completed,
+                            completed_return=completed_return, completed_steps=self.completed_steps,
+                            state_shape=self.state_shape)
+            env.build_obs_alt_ego(self.ego_radius, rows=completed, out=o)
         flat = o.reshape(E * A, *o.shape[2:])
         if self.hidden is None:
             q = agent(flat)
@@ -112,7 +138,7 @@ class QmixCycleCollector(Graphed):
             # an exploring agent never ran its network: its hidden state stays (qmix/trainer.py:251-260)
             self.hidden.copy_(torch.where(self.explored.bool().unsqueeze(1), self.hidden, new_hidden))
         env.step(self.u, auto_reset=False, out=(self.r_env, self.r_shaped, self.done))
-        env.build_obs_alt(out={"idq_obs": o2, "qmix_state": s2}, state_shape=self.state_shape)
+        self._observe(o2, s2)
         self.replay.add(s, s2, o, o2, self.u, self.r_env, self.done)
         self.cur = 1 - c
 

@@ -16,6 +16,8 @@
                     mask with that share of the envs set (1 = all set: the mask's own cost)
   --ego-collect     E, with --ego-radius and --config 5: one QmixCollector(ego_radius=R).collect(graph=True)
                     of E envs on config 5's shape with a linear agent, instead of the builder's times
+  --alt-ego-radius  R (or several), with --config 5: build_obs_alt_ego (all envs, and masks of 1/2 and 1/8 of them)
+                    beside build_obs_ego in float32 and the full idq_obs build, in one process
   --config alt      IDQ/qmix featurizers (§8(f)2)
   --config greedy   batched greedy baseline (§8(f)3)
   --qmix            QMIX episode collection: the masked step against the full step, and one collector
@@ -315,6 +317,78 @@ def run_ego(cfg, radii, steps, warmup, rounds=3, active=()):
     res["full_map_float32"]["us_all_envs"] = [x * nchunks for x in t["full_map_float32"]]
     print(json.dumps({"config": cfg + ":ego", "envs": E, "agents": A, "packages": P, "map": [H, H], "radii": list(radii),
                       "rounds": rounds, "replays": reps, "calls_per_graph": C, "builds": res}), flush=True)
+    env.close()
+
+
+def run_alt_ego(radii, steps, warmup, rounds=3, active=(0.5, 0.125)):
+    """Robot-centred IDQ / map-QMIX windows ("Egocentric IDQ windows") on config 5's shard shape
+    (synthetic 64x64, A = 16, P = 100, 16,384 envs, the IDQ / qmix trainers' fresh tracker): in one process, on
+    one engine, at each radius ``build_obs_alt_ego`` over all envs, the same under ``ego_mask`` at the shares
+    ``active`` and ``build_obs_ego`` in float32 (the same bytes from the 0/1-only kernel), beside the full
+    ``build_obs_alt(which=("idq_obs",))`` per chunk of 4,096 envs, scaled to the shard.  Every figure is a
+    hipGraph of 10 captured calls, each graph captured once and replayed in turn, ``rounds`` times."""
+    import marl_gpu
+    from marl_gpu.maps import grid_array, load_map, map_path
+    dev = torch.device("cuda", 0)
+    E, A, P, T, H = 131072 // 8, 16, 100, 500, 64
+    env = marl_gpu.BatchedEnv(grid_array(load_map(map_path("synthetic64.txt"))), E, A, P, T, seed=7, tracker="fresh",
+                              max_other_robots=15, max_packages_obs=20, max_robots_state=16, max_packages_state=100)
+    chunk = int(os.environ.get("MDL_OBS_CHUNK", "4096"))
+    env.reset()
+    gen = torch.Generator(device=dev).manual_seed(0)
+    G, C = 50, 10
+    acts = torch.randint(0, 15, (G, E, A), generator=gen, device=dev, dtype=torch.int32).to(torch.uint8)
+    for k in range(warmup):
+        env.step(acts[k % G])
+    nchunks = E // chunk
+    full = {"idq_obs": torch.empty((chunk, A, 6, H, H), dtype=torch.float32, device=dev)}
+
+    def full_():
+        for k in range(C):
+            env.build_obs_alt((k % nchunks) * chunk, chunk, out=full, which=("idq_obs",))
+
+    graphs = {"full_idq_obs": (_graph_of(full_), None, chunk * A * 6 * H * H * 4)}
+    keep = [full]   # what the graphs write: a replay after its tensor was freed writes through a stale address
+    for R in radii:
+        K = 2 * R + 1
+        buf = torch.empty((E, A, 6, K, K), dtype=torch.float32, device=dev)
+        keep.append(buf)
+        nbytes = buf.numel() * 4
+
+        def alt_(buf=buf, R=R, rows=None):
+            for k in range(C):
+                env.build_obs_alt_ego(R, rows=rows, out=buf)
+
+        def ego_(buf=buf, R=R):
+            for k in range(C):
+                env.build_obs_ego(R, out=buf)
+
+        graphs[f"alt_ego_r{R}"] = (_graph_of(alt_), None, nbytes)
+        for frac in active:
+            rows = torch.from_numpy(ego_mask(E, frac)).to(dev)
+            graphs[f"alt_ego_r{R}_masked_{frac:g}"] = (_graph_of(lambda f=alt_, rows=rows: f(rows=rows)), rows,
+                                                       nbytes // E * int(rows.sum()))
+        graphs[f"ego_r{R}_float32"] = (_graph_of(ego_), None, nbytes)
+    reps = max(1, steps // 50)
+    t = {k: [] for k in graphs}
+    for _ in range(rounds):
+        for k, (g, _, _) in graphs.items():
+            t[k].append(_replay_us(g, reps, C))
+    res = {}
+    for k, (_, rows, b) in graphs.items():
+        best = min(t[k])
+        res[k] = {"us_per_call": t[k], "envs_per_call": chunk if k.startswith("full") else E, "bytes_written": b,
+                  **({"envs_set": int(rows.sum())} if rows is not None else {}),
+                  "achieved_GBs": b / (best * 1e-6) / 1e9, "frac_of_8TBs": b / (best * 1e-6) / 1e9 / HBM}
+    res["full_idq_obs"]["us_all_envs"] = [x * nchunks for x in t["full_idq_obs"]]
+    full_all = min(res["full_idq_obs"]["us_all_envs"])
+    for R in radii:
+        best = min(t[f"alt_ego_r{R}"])
+        res[f"alt_ego_r{R}"]["of_full_idq_obs"] = best / full_all
+        res[f"alt_ego_r{R}"]["of_ego_float32"] = best / min(t[f"ego_r{R}_float32"])
+    print(json.dumps({"config": "5:alt_ego", "envs": E, "agents": A, "packages": P, "map": [H, H], "radii": list(radii),
+                      "rounds": rounds, "replays": reps, "calls_per_graph": C, "builds": res}), flush=True)
+    del graphs, keep
     env.close()
 
 
@@ -1229,7 +1303,14 @@ def main():
     ap.add_argument("--ego-collect", type=int, default=0,
                     help="with --ego-radius and --config 5: time QmixCollector(ego_radius=R).collect(graph=True) at "
                          "this many envs instead of the builder (one radius, no --ego-active)")
+    ap.add_argument("--alt-ego-radius", default="",
+                    help="with --config 5: a window radius 1..15 (or several, comma-separated); time "
+                         "build_obs_alt_ego (all envs, and under masks of 1/2 and 1/8 of them) beside build_obs_ego "
+                         "in float32 and the full idq_obs build")
     a = ap.parse_args()
+    alt_radii = [int(x) for x in a.alt_ego_radius.split(",") if x]
+    if any(not 1 <= r <= 15 for r in alt_radii) or (alt_radii and a.config != "5"):
+        ap.error(f"--alt-ego-radius: {a.alt_ego_radius!r} (1..15, with --config 5)")
     radii = [int(x) for x in a.ego_radius.split(",") if x]
     if any(not 1 <= r <= 15 for r in radii):
         ap.error(f"--ego-radius: {a.ego_radius!r} (1..15)")
@@ -1255,6 +1336,9 @@ def main():
         return
     if a.qmix_cycle:
         run_qmix_cycle(a.steps)
+        return
+    if alt_radii:
+        run_alt_ego(alt_radii, a.steps, a.warmup)
         return
     for c in a.config.split(","):
         if c == "1":
