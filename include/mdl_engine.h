@@ -143,7 +143,10 @@ int mdl_step_obs(MdlEngine* eng, const uint8_t* actions, int32_t action_format, 
  * pointers may be NULL.  Where mdl_step_obs is one kernel (the small builder, A <= 8, P <= 64)
  * this is one kernel too (an inactive env's wave reads its mask byte and leaves); otherwise a
  * fixed sequence of launches (mask -> id list, the subset step, mask update, the builder over the
- * stepped rows), also without host synchronisation, so either form can be captured in a hipGraph. */
+ * stepped rows), also without host synchronisation, so either form can be captured in a hipGraph.
+ * An engine whose envs mix map shapes is accepted only with all four observation pointers NULL (the
+ * step alone, by that fixed sequence: follow it with mdl_build_obs_canvas and the window builders under
+ * `filled`); with any observation pointer it fails with a message, as no such tensor has one shape. */
 int mdl_step_episode(MdlEngine* eng, const uint8_t* actions, int32_t action_format, uint8_t* active, double* r_env,
                      float* r_shaped, uint8_t* done, uint8_t* filled, float* actor_map, float* actor_vec,
                      float* critic_map, float* critic_vec, void* stream);
@@ -566,6 +569,29 @@ int mdl_build_obs_ego_masked(MdlEngine* eng, int32_t env_begin, int32_t n, const
  * (mdl_views_alt_features) have no window form. */
 int mdl_build_obs_alt_ego(MdlEngine* eng, int32_t env_begin, int32_t n, const uint8_t* rows /* NULL: every env */,
                           int32_t radius, float* idq_ego, void* stream);
+
+/* The critic's (or mixer's) observations of envs of several map shapes at once: the critic map on a fixed
+ * canvas, and the two vector observations, whose row sizes do not depend on the map.
+ * For a canvas (Hc, Wc) = (canvas_h, canvas_w), anchored at the map's top-left cell, and an env of an H x W map:
+ *   critic_canvas [n][4][Hc][Wc],  canvas[ch][i][j] = critic_map[ch][i][j]   for i < H and j < W
+ *                                                   = 1.0 in channel 0, 0.0 in channels 1-3 elsewhere
+ * (critic_map: exactly what mdl_build_obs writes for the same state, tracker mode and clock; an off-map
+ * cell reads as an obstacle, the windows' rule).  With (Hc, Wc) == (H, W) it is critic_map byte for byte.
+ *   actor_vec [n][A][6+5MO+5MP+1], critic_vec [n][6MR+7MPs+1]: each env's rows bit for bit what
+ * mdl_build_obs_as writes for that env, normalised by its own map's H and W.
+ * dtype: MDL_OBS_*, a half element being the float32 value rounded once.  Each output pointer may be NULL.
+ * The range is checked against [0, E) only and may cross map shapes.  The canvas is one launch over the
+ * range; the vectors take the builders' launch once per run of consecutive same-shape envs of the range.
+ * rows: NULL (every env of the range), or DEVICE uint8 [E] indexed by ENV ID (rows[e] for env e, not by
+ * the output row e - env_begin); non-zero = build.  The output rows of env e are at row e - env_begin
+ * either way; rows of unmarked envs are not written, not one byte, in all three tensors.
+ * Asynchronous on `stream`, no host round trip: the call can be captured in a hipGraph.  n == 0 succeeds
+ * and launches nothing.  No cropping: a canvas smaller than a map of the range in either dimension fails
+ * with a message, as do Hc or Wc outside [1, 255], Hc * Wc > MDL_MAX_CELLS, an unknown dtype and an LDS
+ * slice that does not fit; the engine stays usable. */
+int mdl_build_obs_canvas(MdlEngine* eng, int32_t env_begin, int32_t n, const uint8_t* rows /* NULL: every env */,
+                         int32_t dtype, int32_t canvas_h, int32_t canvas_w, void* actor_vec, void* critic_canvas,
+                         void* critic_vec, void* stream);
 
 /* State snapshot into caller DEVICE buffers (async on `stream`).  Any pointer may be NULL.
  *   robots   int32 [E][A][3]  (row, col, carrying), 0-indexed

@@ -170,6 +170,7 @@ struct MdlEngine {
     // shape_run_end[e]: end (exclusive) of env e's run of consecutive envs whose maps share one
     // (H, W); an observation range must lie inside one run (its output tensors have one shape)
     std::vector<int32_t> shape_run_end;
+    std::vector<int32_t> env_map_host;   // each env's map (the host's copy of p.env_map; all 0 without one)
     // greedy baseline (mdl_greedy_*): BFS tables per map and one agent record per env, made on first use
     uint16_t* gtab = nullptr;
     unsigned char* gstate = nullptr;
@@ -486,6 +487,8 @@ int mdl_create(const MdlConfig* cfg, const uint8_t* grids, const int32_t* map_hw
         eng->cfg_fp = h;
     }
     eng->shape_run_end.assign(c.n_envs, c.n_envs);
+    eng->env_map_host.assign(c.n_envs, 0);
+    if (env_map) eng->env_map_host.assign(env_map, env_map + c.n_envs);
     for (int e = c.n_envs - 2; e >= 0; e--) {
         const int m0 = env_map ? env_map[e] : 0, m1 = env_map ? env_map[e + 1] : 0;
         const bool same = eng->mapH[m0] == eng->mapH[m1] && eng->mapW[m0] == eng->mapW[m1];
@@ -673,11 +676,16 @@ int mdl_step_episode(MdlEngine* eng, const uint8_t* actions, int32_t action_form
     if (action_format != MDL_ACTION_TRAINER_INT && action_format != MDL_ACTION_CODES)
         return fail("mdl_step_episode: unknown action_format %d", action_format);
     const int E = eng->p.E;
-    if (eng->shape_run_end[0] < E)
+    // Mixed map shapes: the step alone (no observation tensor has one shape there; mdl_build_obs_canvas and
+    // the window builders follow it).  It takes the launch sequence below, whose step kernel reads each
+    // env's own MapDesc (what mdl_step with env_ids runs on such an engine); the one-launch form is not
+    // taken: its slice and planes are laid out for one shape.
+    const bool mixed = eng->shape_run_end[0] < E;
+    if (mixed && (actor_map || actor_vec || critic_map || critic_vec))
         return fail("mdl_step_episode: the envs mix map shapes (same-shape run ends at %d)", eng->shape_run_end[0]);
     DeviceGuard dg(eng->device);
     hipStream_t s = (hipStream_t)stream;
-    if (const size_t lds = eng->fused_obs_lds()) {
+    if (const size_t lds = mixed ? 0 : eng->fused_obs_lds()) {
         const int wpb = step_wpb(E, eng->n_cu, lds, eng->p.P);
         HIPCHK(mdl::launch_step_episode(eng->p, actions, action_format, E, active, r_env, r_shaped, done, filled,
                                         actor_map, actor_vec, critic_map, critic_vec, wpb, lds, s));
@@ -1155,6 +1163,52 @@ int mdl_build_obs_alt_ego(MdlEngine* eng, int32_t env_begin, int32_t n, const ui
     DeviceGuard dg(eng->device);
     HIPCHK(mdl::launch_alt_ego(eng->p, env_begin, n, rows, radius, idq_ego, waves_per_block(lds), lds, G,
                                (hipStream_t)stream));
+    return 0;
+}
+
+int mdl_build_obs_canvas(MdlEngine* eng, int32_t env_begin, int32_t n, const uint8_t* rows, int32_t dtype,
+                         int32_t canvas_h, int32_t canvas_w, void* actor_vec, void* critic_canvas, void* critic_vec,
+                         void* stream) {
+    const char* who = "mdl_build_obs_canvas";
+    if (!eng) return fail("%s: null engine", who);
+    if (!obs_dtype_ok(dtype)) return fail("%s: unknown observation dtype %d (MDL_OBS_F32 / F16 / BF16)", who, dtype);
+    if (canvas_h < 1 || canvas_w < 1 || canvas_h > 255 || canvas_w > 255 || canvas_h * canvas_w > MDL_MAX_CELLS)
+        return fail("%s: canvas %d x %d: Hc, Wc must be in [1,255] with Hc*Wc <= %d", who, canvas_h, canvas_w,
+                    MDL_MAX_CELLS);
+    // any envs of [0, E): the canvas has one shape whatever the maps, the vectors' rows do not depend on them
+    if (env_begin < 0 || n < 0 || env_begin + n > eng->p.E) return fail("%s: env range out of bounds", who);
+    if (n == 0) return 0;
+    const int end = env_begin + n;
+    for (int b = env_begin; b < end; b = eng->shape_run_end[b]) {   // no cropping: every map of the range fits
+        const int m = eng->env_map_host[b], H = eng->mapH[m], W = eng->mapW[m];
+        if (H > canvas_h || W > canvas_w)
+            return fail("%s: canvas %d x %d is smaller than the %d x %d map of env %d", who, canvas_h, canvas_w, H, W,
+                        b);
+    }
+    const size_t lds = mdl::canvas_lds(eng->p.P, eng->maxHW, canvas_h, canvas_w);
+    if (critic_canvas && lds > LDS_BUDGET)
+        return fail("%s: the canvas needs %zu bytes of LDS per env, more than %zu", who, lds, LDS_BUDGET);
+    DeviceGuard dg(eng->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (critic_canvas)   // one launch over the whole range: every wave reads its own env's map
+        HIPCHK(mdl::launch_canvas(eng->p, env_begin, n, rows, canvas_h, canvas_w, dtype, critic_canvas,
+                                  waves_per_block(lds), lds, s));
+    if (actor_vec || critic_vec) {
+        // The vectors: the builders as they are, one launch per same-shape run (the small builder stages
+        // the rank table of the launch's first env's map).  The builders index their mask by output row:
+        // a run that begins at env b gets rows + b, so that `rows` stays indexed by env id.
+        const size_t es = dtype == MDL_OBS_F32 ? 4 : 2;
+        const size_t av_row = (size_t)eng->p.A * (size_t)(6 + 5 * eng->p.MO + 5 * eng->p.MP + 1) * es;
+        const size_t cv_row = (size_t)(6 * eng->p.MR + 7 * eng->p.MPs + 1) * es;
+        for (int b = env_begin; b < end;) {
+            const int e1 = std::min(end, (int)eng->shape_run_end[b]);
+            const size_t off = (size_t)(b - env_begin);
+            HIPCHK(eng->launch_obs(b, e1 - b, nullptr, actor_vec ? (char*)actor_vec + off * av_row : nullptr, nullptr,
+                                   critic_vec ? (char*)critic_vec + off * cv_row : nullptr, s,
+                                   rows ? rows + b : nullptr, dtype));
+            b = e1;
+        }
+    }
     return 0;
 }
 

@@ -1467,6 +1467,8 @@ __global__ __launch_bounds__(256) void k_obs_h(DevParams p, int env_begin, int n
 #include "mdl_ego.hpp"
 // the same windows of the IDQ / map-QMIX agent observation (k_alt_ego), on mdl_ego.hpp's bit helpers
 #include "mdl_alt_ego.hpp"
+// the critic map on a fixed canvas (k_canvas_maps), on mdl_ego.hpp's bit helpers and emitters
+#include "mdl_canvas.hpp"
 
 // ------------------------------------------------------ dict views (helpers)
 // record: [t, A, n_slots, map] + A*(r, c, carry) + n_slots*(id, status, sr, sc, tr, tc, st, dl)
@@ -2510,6 +2512,35 @@ hipError_t launch_ego(const DevParams& p, int env_begin, int n, const uint8_t* r
             else
                 hipLaunchKernelGGL((k_ego_maps<ST, OT>), g, b, lds * wpb, s, p, env_begin, n, R, (OT*)out, wpb,
                                    (int)lds, G);
+        });
+    };
+    with_int<0, 1>(p.stale != 0, [&](auto st) {
+        if (dtype == OBS_F32) go(st, float{});
+        else if (dtype == OBS_F16) go(st, f16_t{});
+        else go(st, bf16_t{});
+    });
+    return hipGetLastError();
+}
+
+// ---- the canvas builder (mdl_canvas.hpp) ----
+size_t canvas_lds(int P, int maxHW, int Hc, int Wc) { return canvas_lds_bytes(P, maxHW, Hc, Wc); }
+
+hipError_t launch_canvas(const DevParams& p, int env_begin, int n, const uint8_t* rows, int Hc, int Wc, int dtype,
+                         void* out, int wpb, size_t lds, hipStream_t s) {
+    if (dtype != OBS_F32 && dtype != OBS_F16 && dtype != OBS_BF16) return hipErrorInvalidValue;
+    if (Hc < 1 || Wc < 1 || Hc > 255 || Wc > 255 || wpb < 1 || lds < canvas_lds_bytes(p.P, 0, Hc, Wc))
+        return hipErrorInvalidValue;
+    const dim3 g(blocks_for(n, wpb)), b(256);
+    auto go = [&](auto st, auto ot) {   // the tracker mode and element type chosen, the mask's form here
+        constexpr bool ST = decltype(st)::value != 0;
+        using OT = decltype(ot);
+        with_int<0, 1>(rows != nullptr, [&](auto mk) {
+            if constexpr (decltype(mk)::value != 0)
+                hipLaunchKernelGGL((k_masked_canvas_maps<ST, OT>), g, b, lds * wpb, s, p, env_begin, n, Hc, Wc,
+                                   (OT*)out, wpb, (int)lds, rows);
+            else
+                hipLaunchKernelGGL((k_canvas_maps<ST, OT>), g, b, lds * wpb, s, p, env_begin, n, Hc, Wc, (OT*)out,
+                                   wpb, (int)lds);
         });
     };
     with_int<0, 1>(p.stale != 0, [&](auto st) {

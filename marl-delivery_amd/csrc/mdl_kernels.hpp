@@ -81,6 +81,13 @@ int alt_ego_group(int A, int P, int maxHW, int R, size_t budget);
 size_t alt_ego_lds(int A, int P, int maxHW, int G, int R);
 hipError_t launch_alt_ego(const DevParams& p, int env_begin, int n, const uint8_t* rows, int R, float* out, int wpb,
                           size_t lds, int G, hipStream_t s);
+// The critic map on a fixed canvas (k_canvas_maps, mdl_canvas.hpp): out [n][4][Hc][Wc] of `dtype` for envs
+// [env_begin, env_begin + n) of any map shapes, each no larger than the canvas (the caller checks it; a
+// larger map is cropped, not overrun).  canvas_lds: the per-wave slice for maps of up to maxHW cells.
+// rows as launch_ego's (null: every env of the range, k_canvas_maps; else k_masked_canvas_maps).
+size_t canvas_lds(int P, int maxHW, int Hc, int Wc);
+hipError_t launch_canvas(const DevParams& p, int env_begin, int n, const uint8_t* rows, int Hc, int Wc, int dtype,
+                         void* out, int wpb, size_t lds, hipStream_t s);
 // A launch's own completion word (host-mapped): every wave of its grid counts itself in the
 // running device counter `ctr` (never reset: `base` is its value before the launch) after a
 // system-scope release of its stores; the last one writes `value` to `seq`.  seq == nullptr: none;

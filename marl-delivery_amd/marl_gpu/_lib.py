@@ -30,6 +30,7 @@ MDL_ACTION_TRAINER_INT = 0
 MDL_ACTION_CODES = 1
 MDL_MAX_ROBOTS = 64
 MDL_MAX_PACKAGES = 1024
+MDL_MAX_CELLS = 16384
 MDL_REPLAY_MAX_ENVS = 65536
 MDL_OBS_BUILDER_AUTO = 0
 MDL_OBS_BUILDER_GENERIC = 1
@@ -91,6 +92,7 @@ SIGNATURES = {
     "mdl_build_obs_as": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "mdl_build_obs_ego": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "mdl_build_obs_ego_masked": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp]),
+    "mdl_build_obs_canvas": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "mdl_build_obs_alt": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp]),
     "mdl_build_obs_alt_ego": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _vp, _vp]),
     "mdl_alt_pre_bytes": (C.c_int, [_vp, C.POINTER(C.c_int64)]),

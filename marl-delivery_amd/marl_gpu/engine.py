@@ -366,7 +366,11 @@ class BatchedEnv:
         launch where ``step_obs`` is one.  A done env's byte is cleared on the device.  The other
         envs are not touched: their r_env / r_shaped / done / ``filled`` are 0 and their rows of
         ``obs_out`` are left unwritten.  Never resets.  Returns (r_env, r_shaped, done, obs dict);
-        ``filled`` (uint8 [E]) receives 1 for the envs that were stepped."""
+        ``filled`` (uint8 [E]) receives 1 for the envs that were stepped.
+
+        An engine whose envs mix map shapes takes ``which=()`` only (the step alone; the dict's entries
+        are None): ``build_obs_canvas(rows=filled)`` and ``build_obs_ego_masked(filled)`` write the
+        observations of such a batch.  With an observation named it raises, as on any mixed engine."""
         n = self.E
         if actions.dtype is not torch.uint8 or not actions.is_cuda or not actions.is_contiguous() \
                 or actions.get_device() != self._dev or actions.numel() != n * self.A:
@@ -379,8 +383,12 @@ class BatchedEnv:
             ptrs = (out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr())
         else:
             ptrs = self._out_ptrs(out, (n,))
-        H, W = self.single_map_shape("step_episode")
-        obs_out, op = self._obs_out(obs_out, which, n, H, W)
+        if not which and self._shape_run_end[0] < self.E:
+            # mixed map shapes: the step alone (build_obs_canvas and the window builders follow it)
+            obs_out, op = dict.fromkeys(OBS_KEYS), [None] * 4
+        else:
+            H, W = self.single_map_shape("step_episode")
+            obs_out, op = self._obs_out(obs_out, which, n, H, W)
         check(lib().mdl_step_episode(self._h, actions.data_ptr(), ACTION_FORMATS[action_format], active.data_ptr(),
                                      ptrs[0], ptrs[1], ptrs[2], ptr(filled), *op, _raw_stream(self._dev)),
               "mdl_step_episode")
@@ -621,6 +629,79 @@ class BatchedEnv:
         else:
             check(lib().mdl_build_obs_ego_masked(self._h, env_begin, n, ptr(rows), R, dt, ptr(out), self._stream()),
                   "mdl_build_obs_ego_masked")
+        return out
+
+    # ---- the critic map on a fixed canvas: observations of envs of several map shapes ----
+    CANVAS_KEYS = ("actor_vec", "critic_map", "critic_vec")
+
+    def _canvas(self, canvas):
+        try:
+            Hc, Wc = canvas
+            ok = all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in (Hc, Wc))
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f"canvas must be a pair of ints (Hc, Wc), not {canvas!r}")
+        Hc, Wc = int(Hc), int(Wc)
+        if not (1 <= Hc <= 255 and 1 <= Wc <= 255 and Hc * Wc <= _lib.MDL_MAX_CELLS):
+            raise ValueError(f"canvas {Hc} x {Wc}: Hc, Wc must be in [1, 255] with Hc * Wc <= {_lib.MDL_MAX_CELLS}")
+        return Hc, Wc
+
+    def canvas_buffers(self, canvas, n=None, dtype: torch.dtype = torch.float32):
+        """New tensors of ``dtype`` for ``build_obs_canvas``: actor_vec [n, A, Dv], critic_map
+        [n, 4, Hc, Wc] and critic_vec [n, Dg] for ``canvas = (Hc, Wc)``."""
+        _obs_dtype(dtype)
+        Hc, Wc = self._canvas(canvas)
+        n = self.E if n is None else int(n)
+        f = dict(dtype=dtype, device=self.device)
+        return dict(actor_vec=torch.empty((n, self.A, self.actor_vec_dim), **f),
+                    critic_map=torch.empty((n, 4, Hc, Wc), **f),
+                    critic_vec=torch.empty((n, self.critic_vec_dim), **f))
+
+    def build_obs_canvas(self, canvas, env_begin: int = 0, n: int | None = None, rows: torch.Tensor | None = None,
+                         out: dict | None = None, which=("actor_vec", "critic_map", "critic_vec"),
+                         dtype: torch.dtype = torch.float32):
+        """The critic's observations of envs [env_begin, env_begin + n) of any map shapes: the critic map
+        on the fixed canvas ``canvas = (Hc, Wc)`` and the two vector observations -> a dict.
+
+        ``critic_map`` is [n, 4, Hc, Wc]: the env's ``build_obs()["critic_map"]`` in its top-left
+        ``[:H, :W]`` corner (cell coordinates stay the ones the vectors carry); elsewhere channel 0
+        (obstacles) is 1.0 and channels 1-3 are 0.0 -- an off-map cell cannot be entered, the windows'
+        rule (``build_obs_ego``).  With ``canvas == (H, W)`` it is ``build_obs``'s tensor byte for byte.
+        ``actor_vec`` [n, A, Dv] and ``critic_vec`` [n, Dg] hold each env's ``build_obs`` rows, normalised
+        by its own map's H and W.  No cropping: the canvas must cover every map of the range, with
+        Hc, Wc <= 255 and Hc * Wc <= 16384.
+
+        ``rows``: None (every env of the range), or uint8 [E] on the engine's device indexed by env id
+        whatever the range (``step_episode``'s ``filled``); the rows of unmarked envs are not written in
+        any of the three tensors.  ``which``, ``out`` and ``dtype`` as ``build_obs``.  One launch for the
+        canvas and one per same-shape run of the range for the vectors, none of them synchronising with
+        the host: the call can be captured in a hipGraph."""
+        dt = _obs_dtype(dtype)
+        Hc, Wc = self._canvas(canvas)
+        env_begin = int(env_begin)
+        n = self.E - env_begin if n is None else int(n)
+        if env_begin < 0 or n < 0 or env_begin + n > self.E:
+            raise IndexError(f"env range [{env_begin}, {env_begin + n}) outside [0, {self.E})")
+        if rows is not None:
+            self._check_mask(rows, "rows")
+        if out is None:
+            out = self.canvas_buffers((Hc, Wc), n, dtype)
+            if rows is not None:   # unmarked rows of a fresh tensor read as zeros
+                for t in out.values():
+                    t.zero_()
+        shapes = dict(actor_vec=(n, self.A, self.actor_vec_dim), critic_map=(n, 4, Hc, Wc),
+                      critic_vec=(n, self.critic_vec_dim))
+        op = []
+        for k in self.CANVAS_KEYS:
+            t = out[k] if k in which else None
+            if t is not None:
+                self._check_obs_out(t, k, shapes[k], dtype)
+            op.append(ptr(t))
+        if n == 0:
+            return out
+        check(lib().mdl_build_obs_canvas(self._h, env_begin, n, ptr(rows), dt, Hc, Wc, *op, self._stream()),
+              "mdl_build_obs_canvas")
         return out
 
     # ---- IDQ / qmix featurizers (SURVEY.md §8(f)2) ----

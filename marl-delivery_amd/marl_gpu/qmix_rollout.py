@@ -56,21 +56,32 @@ class QmixCollector(Graphed):
     step while its terminal observation is still due, as the full-map path writes it.  Rows past an
     episode's end stay unwritten, as in the full-map form.  ego_radius=None (the default): nothing changes.
 
+    canvas=(Hc, Wc), with ego_radius (ValueError without it): the mixer's state is the critic map on that
+    fixed canvas (``BatchedEnv.build_obs_canvas``: the map in the top-left corner, off-map cells obstacles),
+    gs is [L+1, E, 4, Hc, Wc], and the engine may mix map shapes.  Each step is then three calls:
+    ``step_episode(which=())``, ``build_obs_canvas(rows=filled[t])`` for gs / vo / gv and
+    ``build_obs_ego_masked(filled[t])`` -- both under ``filled``, for the reason above.  The canvas must
+    cover every map.  canvas=None (the default): nothing changes.
+
     One deviation from the reference: the agent also runs on the finished envs (the
     reference shrinks its batch instead).  Their actions and hidden states are ignored --
     the engine does not step them -- so the finished envs cost forward-pass time only.
     """
 
     def __init__(self, env, episode_limit: int, seed: int = 0, avail: bool = False, ego_radius: int | None = None,
-                 ego_dtype: torch.dtype = torch.float32):
+                 ego_dtype: torch.dtype = torch.float32, canvas=None):
         self.env = env
+        if canvas is not None and ego_radius is None:
+            raise ValueError("QmixCollector: canvas needs ego_radius (the agent's full map has no shape "
+                             "common to several maps)")
+        self.canvas = None if canvas is None else env._canvas(canvas)
         self.L = L = min(int(episode_limit), env.T)
         if L < 1:
             raise ValueError("QmixCollector: episode_limit must be >= 1")
         self.seed = int(seed)
         self._init_graphs(env.device)
         E, A = env.E, env.A
-        H, W = env.single_map_shape("QmixCollector")
+        H, W = env.single_map_shape("QmixCollector") if self.canvas is None else self.canvas
         dev = env.device
         f = dict(dtype=torch.float32, device=dev)
         b = dict(dtype=torch.uint8, device=dev)
@@ -150,7 +161,11 @@ class QmixCollector(Graphed):
         R = self.ego_radius
         which = ("actor_map", "actor_vec", "critic_map", "critic_vec") if R is None else \
             ("actor_vec", "critic_map", "critic_vec")
-        env.build_obs(out=self._slot(0), which=which)
+        cv = self.canvas
+        if cv is None:
+            env.build_obs(out=self._slot(0), which=which)
+        else:
+            env.build_obs_canvas(cv, out=self._slot(0))
         if R is not None:
             env.build_obs_ego(R, out=self.so[0], dtype=self.ego_dtype)
         masks = self.avail
@@ -170,8 +185,13 @@ class QmixCollector(Graphed):
             else:
                 select_actions_eps(q, epsilon, self.seed, self.offset, avail=av, out=self.u[t].view(-1))
             self.offset += 1
-            env.step_episode(self.u[t], self.active, out=(self.r64[t], self.r_shaped[t], self.terminated[t]),
-                             filled=self.filled[t], obs_out=self._slot(t + 1), which=which)
+            if cv is None:
+                env.step_episode(self.u[t], self.active, out=(self.r64[t], self.r_shaped[t], self.terminated[t]),
+                                 filled=self.filled[t], obs_out=self._slot(t + 1), which=which)
+            else:   # any map shapes: the step alone, then the stepped envs' canvas and vectors
+                env.step_episode(self.u[t], self.active, out=(self.r64[t], self.r_shaped[t], self.terminated[t]),
+                                 filled=self.filled[t], which=())
+                env.build_obs_canvas(cv, rows=self.filled[t], out=self._slot(t + 1))
             if R is not None:   # the envs this step moved, those that just finished included
                 env.build_obs_ego_masked(R, self.filled[t], out=self.so[t + 1], dtype=self.ego_dtype)
             if masks is not None:

@@ -68,13 +68,25 @@ class MappoRollout(Graphed):
     ``mb_obs`` and ``next_obs["actor_map"]`` are [.., A, 6, K, K] in ``obs_dtype``, the actor receives
     obs [E*A, 6, K, K], and every step is ``step_obs`` of the other three tensors followed by
     ``build_obs_ego`` into the next slot (the first observation likewise).  The critic keeps the full
-    map, so the envs must still share one map shape.
+    map, so the envs must still share one map shape -- unless ``canvas`` is given.
+
+    canvas: None (the default: nothing changes), or (Hc, Wc) with ``ego_radius`` (ValueError without it)
+    -- the critic then sees its map on that fixed canvas (``BatchedEnv.build_obs_canvas``: the map in the
+    top-left corner, off-map cells obstacles), so the engine may mix map shapes: one policy collects on
+    several maps at once.  ``mb_global_states`` and ``next_obs["critic_map"]`` are [.., 4, Hc, Wc], the
+    critic receives gmap [E, 4, Hc, Wc], and every step is ``step(auto_reset=True)``,
+    ``build_obs_canvas`` into the next slot, then ``build_obs_ego``.  The canvas must cover every map.
     """
 
     def __init__(self, env, rollout_steps: int, seed: int = 0, gamma: float = 0.99, gae_lambda: float = 0.95,
-                 avail: bool = False, obs_dtype: torch.dtype = torch.float32, ego_radius: int | None = None):
+                 avail: bool = False, obs_dtype: torch.dtype = torch.float32, ego_radius: int | None = None,
+                 canvas=None):
         self.env = env
         self.ego_radius = None if ego_radius is None else env._ego_radius(ego_radius)
+        if canvas is not None and self.ego_radius is None:
+            raise ValueError("MappoRollout: canvas needs ego_radius (the actor's full map has no shape "
+                             "common to several maps)")
+        self.canvas = None if canvas is None else env._canvas(canvas)
         if obs_dtype not in (torch.float32, torch.float16, torch.bfloat16):
             raise TypeError(f"obs_dtype must be torch.float32, torch.float16 or torch.bfloat16, not {obs_dtype}")
         self.obs_dtype = obs_dtype
@@ -83,7 +95,7 @@ class MappoRollout(Graphed):
         self._init_graphs(env.device)
         self.gamma, self.gae_lambda = gamma, gae_lambda
         E, A = env.E, env.A
-        H, W = env.single_map_shape("MappoRollout")
+        H, W = env.single_map_shape("MappoRollout") if self.canvas is None else self.canvas
         dev = env.device
         f = dict(dtype=torch.float32, device=dev)
         T = self.T
@@ -101,7 +113,10 @@ class MappoRollout(Graphed):
         self.mb_rewards = torch.zeros((T, E), **f)
         self.mb_dones = torch.zeros((T, E), dtype=torch.uint8, device=dev)
         self.mb_values = torch.zeros((T, E), **f)
-        self.next_obs = env.obs_buffers(E, H, W, obs_dtype)
+        if self.canvas is None:
+            self.next_obs = env.obs_buffers(E, H, W, obs_dtype)
+        else:
+            self.next_obs = env.canvas_buffers(self.canvas, E, obs_dtype)
         if self.ego_radius is not None:
             self.next_obs["actor_map"] = env.ego_buffers(self.ego_radius, E, obs_dtype)
         self._r_env = torch.zeros(E, dtype=torch.float64, device=dev)
@@ -140,7 +155,11 @@ class MappoRollout(Graphed):
         # with a radius the actor map is the window builder's
         which = ("actor_vec", "critic_map", "critic_vec") if R is not None else \
             ("actor_map", "actor_vec", "critic_map", "critic_vec")
-        env.build_obs(out=self._slot(0), which=which, dtype=self.obs_dtype)   # current obs = f(current state, tracker)
+        cv = self.canvas
+        if cv is None:
+            env.build_obs(out=self._slot(0), which=which, dtype=self.obs_dtype)   # current obs = f(current state, tracker)
+        else:
+            env.build_obs_canvas(cv, out=self._slot(0), dtype=self.obs_dtype)
         if R is not None:
             env.build_obs_ego(R, out=self.mb_obs[0], dtype=self.obs_dtype)
         for step in range(T):
@@ -156,9 +175,14 @@ class MappoRollout(Graphed):
             self.mb_values[step] = critic(self.mb_global_states[step], self.mb_global_vector[step]).reshape(E)
             # step + the next observations in one launch (MAPPO/trainer.py:229-286)
             nxt = self._slot(step + 1) if step + 1 < T else self.next_obs
-            env.step_obs(self.mb_actions[step], auto_reset=True,
-                         out=(self._r_env, self.mb_rewards[step], self.mb_dones[step]),
-                         obs_out=nxt, which=which, obs_dtype=self.obs_dtype)
+            if cv is None:
+                env.step_obs(self.mb_actions[step], auto_reset=True,
+                             out=(self._r_env, self.mb_rewards[step], self.mb_dones[step]),
+                             obs_out=nxt, which=which, obs_dtype=self.obs_dtype)
+            else:   # any map shapes: the step, then the canvas and the vectors of the new state
+                env.step(self.mb_actions[step], auto_reset=True,
+                         out=(self._r_env, self.mb_rewards[step], self.mb_dones[step]))
+                env.build_obs_canvas(cv, out=nxt, dtype=self.obs_dtype)
             if R is not None:
                 env.build_obs_ego(R, out=nxt["actor_map"], dtype=self.obs_dtype)
         if dev_offset:

@@ -20,6 +20,9 @@
                     beside build_obs_ego in float32 and the full idq_obs build, in one process
   --config alt      IDQ/qmix featurizers (§8(f)2)
   --config greedy   batched greedy baseline (§8(f)3)
+  --canvas          HC WC: configs 3 / 5 time build_obs_canvas of the critic map (the map's own shape and HC x WC,
+                    float32 and bfloat16, all envs in one call) beside build_obs's critic_map; config 4 times a
+                    graphed mixed-map MappoRollout(ego_radius=5, canvas=) beside the single-shape ego rollout
   --qmix            QMIX episode collection: the masked step against the full step, and one collector
                     step against the host-driven subset loop
   --idq             IDQ transition collection: alt_transition against build_obs_alt, and one collector
@@ -437,6 +440,110 @@ def run_ego_collect(E, R, steps):
         del col
     print(json.dumps({"config": "5:ego_collect", "envs": E, "agents": A, "packages": P, "map": [64, 64], "radius": R,
                       "L": T, "collects_per_round": n, "rounds": 3, "collect": out}), flush=True)
+    env.close()
+
+
+def run_canvas(cfg, canvas, steps, warmup, rounds=3):
+    """The critic map on a fixed canvas ("Canvas critic maps").
+
+    Config 3 or 5: in one process, on one engine, ``build_obs_canvas(canvas, which=("critic_map",))`` over all
+    of the rank's envs in one call, at the map's own shape (the identity) and at ``canvas``, float32 and
+    bfloat16, beside the existing ``build_obs(which=("critic_map",))`` (float32; config 5: per chunk of 4,096
+    envs, as its usual leg builds them).  Every figure is a hipGraph of 10 captured calls, each graph captured
+    once and replayed in turn, ``rounds`` times -- the builds alternate inside one session.
+
+    Config 4: a graphed ``MappoRollout(ego_radius=5, canvas=canvas)`` on its map mix (map1 .. map5) at 4,096
+    envs, per env-step, beside the single-shape ego rollout of the same size on map1."""
+    import marl_gpu
+    from marl_gpu.maps import grid_array, load_map, map_path
+    dev = torch.device("cuda", 0)
+    Hc, Wc = canvas
+    if cfg == "4":
+        import marl_gpu.rollout as R
+        E, A, P, T, Tr = 4096, 5, 50, 500, 64
+        maps = [grid_array(load_map(map_path(f"map{i}.txt"))) for i in range(1, 6)]
+        sizes = [E // 5 + (1 if i < E % 5 else 0) for i in range(5)]
+        env_map = np.concatenate([np.full(s, i) for i, s in enumerate(sizes)])
+        mixed = marl_gpu.BatchedEnv(maps, E, A, P, T, seed=42, env_map=env_map, tracker="mappo", max_packages_obs=5)
+        single = marl_gpu.BatchedEnv(maps[0], E, A, P, T, seed=42, tracker="mappo", max_packages_obs=5)
+        g = torch.Generator(device="cuda").manual_seed(0)
+        wa = torch.randn(mixed.actor_vec_dim, 15, device="cuda", generator=g) * 0.1
+        wc = torch.randn(mixed.critic_vec_dim, device="cuda", generator=g) * 0.01
+        actor = lambda obs, vec: vec @ wa  # noqa: E731
+        critic = lambda gmap, gvec: gvec @ wc  # noqa: E731
+        legs = {"mixed_canvas": R.MappoRollout(mixed, Tr, seed=1, ego_radius=5, canvas=canvas),
+                "single_shape_ego": R.MappoRollout(single, Tr, seed=1, ego_radius=5)}
+        for env in (mixed, single):
+            env.reset()
+        for ro in legs.values():
+            ro.collect(actor, critic, graph=True)   # runs eagerly and captures
+        n = max(1, steps // Tr)
+        t = {k: [] for k in legs}
+        for _ in range(rounds):
+            for k, ro in legs.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(n):
+                    ro.collect(actor, critic, graph=True)
+                torch.cuda.synchronize()
+                t[k].append((time.perf_counter() - t0) / (n * Tr) * 1e6)
+        print(json.dumps({"config": "4:canvas_rollout", "envs": E, "agents": A, "packages": P, "canvas": [Hc, Wc],
+                          "maps": [list(m.shape) for m in maps], "ego_radius": 5, "rollout_steps": Tr, "rollouts": n,
+                          "rounds": rounds, "us_per_env_step": t}), flush=True)
+        mixed.close()
+        single.close()
+        return
+    if cfg == "3":
+        E, A, P, T, H = 16384, 5, 50, 500, 10
+        env = marl_gpu.BatchedEnv(grid_array(load_map(map_path("map1.txt"))), E, A, P, T, seed=42, tracker="mappo",
+                                  max_other_robots=4, max_packages_obs=5)
+        chunk = E
+    elif cfg == "5":
+        E, A, P, T, H = 131072 // 8, 16, 100, 500, 64
+        env = marl_gpu.BatchedEnv(grid_array(load_map(map_path("synthetic64.txt"))), E, A, P, T, seed=7,
+                                  tracker="mappo", max_other_robots=15, max_packages_obs=20, max_robots_state=16,
+                                  max_packages_state=100)
+        chunk = int(os.environ.get("MDL_OBS_CHUNK", "4096"))
+    else:
+        raise SystemExit("--canvas goes with --config 3, 4 or 5")
+    env.reset()
+    gen = torch.Generator(device=dev).manual_seed(0)
+    G, C = 50, 10
+    acts = torch.randint(0, 15, (G, E, A), generator=gen, device=dev, dtype=torch.int32).to(torch.uint8)
+    for k in range(warmup):
+        env.step(acts[k % G])
+    nchunks = E // chunk
+    full = {"critic_map": torch.empty((chunk, 4, H, H), dtype=torch.float32, device=dev)}
+
+    def full_():
+        for k in range(C):
+            env.build_obs((k % nchunks) * chunk, chunk, out=full, which=("critic_map",))
+
+    graphs = {"build_obs_float32": (_graph_of(full_), full, chunk * 4 * H * H * 4)}
+    for cv in dict.fromkeys(((H, H), (Hc, Wc))):
+        for n in ("float32", "bfloat16"):
+            buf = {"critic_map": torch.empty((E, 4) + cv, dtype=OBS_DTYPES[n], device=dev)}
+
+            def canvas_(buf=buf, cv=cv, n=n):
+                for k in range(C):
+                    env.build_obs_canvas(cv, out=buf, which=("critic_map",), dtype=OBS_DTYPES[n])
+
+            graphs[f"canvas_{cv[0]}x{cv[1]}_{n}"] = (_graph_of(canvas_), buf,
+                                                    buf["critic_map"].numel() * buf["critic_map"].element_size())
+    reps = max(1, steps // 50)
+    t = {k: [] for k in graphs}
+    for _ in range(rounds):
+        for k, (g, _, _) in graphs.items():
+            t[k].append(_replay_us(g, reps, C))
+    res = {}
+    for k, (_, _, b) in graphs.items():
+        best = min(t[k])
+        res[k] = {"us_per_call": t[k], "envs_per_call": chunk if k.startswith("build_obs") else E, "bytes_written": b,
+                  "achieved_GBs": b / (best * 1e-6) / 1e9, "frac_of_8TBs": b / (best * 1e-6) / 1e9 / HBM}
+    res["build_obs_float32"]["us_all_envs"] = [x * nchunks for x in t["build_obs_float32"]]
+    print(json.dumps({"config": cfg + ":canvas", "envs": E, "agents": A, "packages": P, "map": [H, H],
+                      "canvas": [Hc, Wc], "rounds": rounds, "replays": reps, "calls_per_graph": C, "builds": res}),
+          flush=True)
     env.close()
 
 
@@ -1307,6 +1414,10 @@ def main():
                     help="with --config 5: a window radius 1..15 (or several, comma-separated); time "
                          "build_obs_alt_ego (all envs, and under masks of 1/2 and 1/8 of them) beside build_obs_ego "
                          "in float32 and the full idq_obs build")
+    ap.add_argument("--canvas", type=int, nargs=2, metavar=("HC", "WC"), default=None,
+                    help="with --config 3 / 5: time build_obs_canvas of the critic map at the map's own shape and at "
+                         "HC x WC beside build_obs's critic_map; with --config 4: a graphed mixed-map "
+                         "MappoRollout(ego_radius=5, canvas=) beside the single-shape ego rollout (4,096 envs)")
     a = ap.parse_args()
     alt_radii = [int(x) for x in a.alt_ego_radius.split(",") if x]
     if any(not 1 <= r <= 15 for r in alt_radii) or (alt_radii and a.config != "5"):
@@ -1350,6 +1461,8 @@ def main():
             run_alt(a.steps)
         elif c == "greedy":
             run_greedy(a.steps)
+        elif a.canvas:
+            run_canvas(c, tuple(a.canvas), a.steps, a.warmup)
         elif radii and a.ego_collect:
             if c != "5" or len(radii) != 1 or active:
                 ap.error("--ego-collect goes with --config 5 and one --ego-radius, without --ego-active")
